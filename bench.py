@@ -13,8 +13,15 @@ N GPUs:      python bench.py --gpus N ...   (starts N ranks itself: parallel/lau
              python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                  --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 Every rank runs on its own GPU; the JSON line (rank 0) reports the whole-job img/s from the
-slowest rank's time, the per-rank ms/step, the measured all-reduce time per averaging and
-an RCCL bus-bandwidth probe of the 244 MB averaging payload at three bucket sizes.
+slowest rank's time, the per-rank ms/step and the measured all-reduce time per averaging.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the JSON line.  ``--full``
+adds the measurements that take runs of their own after the timed window: with N > 1 ranks an
+RCCL bus-bandwidth probe of the 244 MB averaging payload at three bucket sizes (``comm_bench``)
+and the per-bucket all-reduce times (``diag.bucket_allreduce_ms``).  ``--dump-outputs DIR``
+writes what the last timed step left (rank 0): the loss it returned and the fp32 master weights
+it produced, as ``DIR/<name>.npy``; data and initial weights are seeded, so two builds run
+with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -93,6 +100,14 @@ def parse():
                    help="time GEMM products the tuning database lacks on first use (off by default: the "
                         "committed database + cost model give every process and rank the same kernels; with "
                         "N > 1 ranks rank 0's choices are adopted by all before graph capture)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed window also run the extra measurements (N > 1 ranks: the RCCL "
+                        "bus-bandwidth probe comm_bench and the per-bucket all-reduce times of the diag block); "
+                        "off by default: a plain run only measures the headline figure")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write the last step's results as DIR/<name>.npy (float32): the "
+                        "loss, the master weights after it and their change over the timed window (a fixed, "
+                        "seeded sample of the weights where they exceed DUMP_MAX_ELEMS)")
     return p.parse_args()
 
 
@@ -108,6 +123,7 @@ DEFAULTS = {  # model: (batch, channels, src hw, crop, classes, mean, input scal
     "cifar10_full": (100, 3, 32, 32, 10, [125.0, 123.0, 114.0], 1.0),
 }
 HEADLINE = ("caffenet", "alexnet")
+DUMP_MAX_ELEMS = 4 << 20  # per dumped array: 16 MB of float32, 2 sampled arrays + the loss < 64 MB
 
 
 def main():
@@ -213,6 +229,10 @@ def main():
         comm.barrier()
     sync()
 
+    # --dump-outputs: the weights the timed window starts from (untimed copy, before t0)
+    w_start = net.flat_data.detach().clone() if args.dump_outputs and rank == 0 else None
+    sync()
+
     avg_events = []
     step_evs = []
     if args.step_times and dev.type == "cuda":
@@ -247,6 +267,10 @@ def main():
     sync()
     elapsed_rank = time.perf_counter() - t0
     elapsed = elapsed_rank
+    final_loss = float(loss) if loss is not None else float("nan")
+    if w_start is not None:
+        dump_outputs(args.dump_outputs, final_loss, net.flat_data.detach(), w_start)
+        del w_start
     if step_evs:
         ms = [step_evs[i].elapsed_time(step_evs[i + 1]) for i in range(len(step_evs) - 1)]
         print(f"rank {rank} step ms: " + " ".join(f"{v:.2f}" for v in ms), file=sys.stderr, flush=True)
@@ -262,10 +286,10 @@ def main():
         if args.verify_average:  # untimed: average once more so the window's last step is averaged
             trainer.average()
             avg_check = verify_average(comm, net, dev, sync)
-        comm_info = comm_bench(comm, net.flat_data, dev, sync, iters=1 if args.share_gpu else 4)
-        bucket_ms = diag.timed_bucket_allreduce(comm, net.flat_data, comm.average_bucket_bytes, sync)
+        if args.full:
+            comm_info = comm_bench(comm, net.flat_data, dev, sync, iters=1 if args.share_gpu else 4)
+            bucket_ms = diag.timed_bucket_allreduce(comm, net.flat_data, comm.average_bucket_bytes, sync)
         numa_all = comm.allgather_int(int(numa))
-    final_loss = float(loss) if loss is not None else float("nan")
 
     ms = 1000.0 * elapsed / args.steps
     img_s = world * B * args.steps / elapsed
@@ -332,6 +356,28 @@ def main():
     if comm is not None:
         comm.close()
     return 0
+
+
+def dump_outputs(directory, final_loss, weights, w_start):
+    """What a caller of the timed path holds after its last step: the loss that step returned
+    and the fp32 master weights it left, plus their change over the timed window (the sum of
+    the timed steps' updates, which small numerical differences show in far more clearly than
+    in the weights themselves).  Weight buffers above DUMP_MAX_ELEMS elements are sampled at
+    fixed positions: DUMP_MAX_ELEMS sorted draws of a generator seeded with a constant."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    n = weights.numel()
+    np.save(os.path.join(directory, "loss.npy"), np.asarray([final_loss], dtype=np.float32))
+    if n > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(20240607)
+        idx = torch.randint(0, n, (DUMP_MAX_ELEMS,), generator=g).sort().values
+        idx = idx.to(weights.device)
+        w1, w0 = weights.index_select(0, idx), w_start.index_select(0, idx)
+    else:
+        w1, w0 = weights, w_start
+    np.save(os.path.join(directory, "weights.npy"), w1.float().cpu().numpy())
+    np.save(os.path.join(directory, "weights_update.npy"), (w1.float() - w0.float()).cpu().numpy())
 
 
 def verify_average(comm, net, dev, sync):

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--cpu", "--model", "cifar10_quick", "--batch", "4", "--steps", "3", "--warmup", "1", "--tau", "2"]
 
@@ -19,7 +21,8 @@ def _clean_env():
 
 
 def test_bench_spawns_n_ranks_and_reports_job_json():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", *ARGS], cwd=ROOT, env=_clean_env(),
+    # --full: the collective probes (comm_bench, diag.bucket_allreduce_ms) run only on request
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", *ARGS], cwd=ROOT, env=_clean_env(),
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -70,6 +73,8 @@ def test_bench_under_torchrun_like_the_driver():
     assert len(lines) == 1, r.stdout  # rank 0 prints the job line
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["rccl_world"] == 2 and out["config"]["parallelism"] == "dp2"
+    # a plain run measures the headline figure only: no collective probes after the window
+    assert "comm_bench" not in out and out["diag"]["bucket_allreduce_ms"] is None
 
 
 def _free_port():
@@ -87,13 +92,59 @@ def test_bench_forced_comm_at_world_one():
     env["SN_COMM_FORCE"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1",
-                        "--verify-average", *ARGS], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--verify-average", "--full", *ARGS], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["rccl_world"] == 1 and out["comm_backend"] == "gloo"
     assert out["averages_in_window"] >= 1 and out["average_buckets"] >= 1
     assert out["avg_check"]["masters_equal_across_ranks"] and out["avg_check"]["shadow_is_bf16_master"]
     assert set(out["comm_bench"]) == {"bucket_256MB", "bucket_64MB", "bucket_16MB"}
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs: float32 arrays of what the last timed step left (its loss, the master
+    weights, their change over the window), identical from run to run with the same arguments,
+    and the JSON line keeps its headline fields with --steps timed steps."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *ARGS, "--dump-outputs", str(d)], cwd=ROOT,
+                           env=_clean_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "images/sec"
+        assert out["higher_is_better"] is True and out["dtype"] == "fp32-cpu" and "comm_bench" not in out
+        assert out["value"] == pytest.approx(4 * 1000.0 / out["ms_per_step"], rel=1e-2)
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+        assert abs(float(dumps[-1]["loss.npy"][0]) - out["config"]["final_loss"]) <= 1e-4
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["loss.npy", "weights.npy", "weights_update.npy"]
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all()
+        assert np.array_equal(a[k], b[k]), k
+    assert a["weights.npy"].shape == a["weights_update.npy"].shape and np.abs(a["weights_update.npy"]).max() > 0
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+
+
+def test_dump_outputs_samples_large_weight_buffers(tmp_path, monkeypatch):
+    """Weight buffers above DUMP_MAX_ELEMS elements are written as a fixed sample."""
+    import numpy as np
+    import torch
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # bench.py sets it on import: undone after the test
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 1000
+    w0 = torch.arange(n, dtype=torch.float32)
+    w1 = w0 + 1.0
+    bench.dump_outputs(str(tmp_path / "a"), 1.5, w1, w0)
+    bench.dump_outputs(str(tmp_path / "b"), 1.5, w1, w0)
+    a, b = np.load(tmp_path / "a" / "weights.npy"), np.load(tmp_path / "b" / "weights.npy")
+    assert a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b) and (np.diff(a) >= 0).all()
+    assert (np.load(tmp_path / "a" / "weights_update.npy") == 1.0).all()
+    assert 3 * 4 * bench.DUMP_MAX_ELEMS <= 64 << 20
 
 
 def test_comm_inactive_at_world_one_without_force():

@@ -17,11 +17,9 @@ from sparknet_amd.core.net import Net
 from sparknet_amd.core.solver import Solver
 from sparknet_amd.utils import hdf5
 
-FIX = "/root/reference/caffe/src/caffe/test/test_data"
-need_fixtures = pytest.mark.skipif(not os.path.isdir(FIX), reason="reference fixtures not present")
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hdf5")  # copies of those three files
 
 
-@need_fixtures
 def test_read_reference_fixtures():
     f = hdf5.File(f"{FIX}/sample_data.h5")
     assert f.keys() == ["data", "label", "label2"]
@@ -69,7 +67,6 @@ def test_writer_roundtrip(tmp_path):
     assert "grp/layer05/1" in f and "grp/nope" not in f
 
 
-@need_fixtures
 def test_hdf5_data_layer_matches_reference_test(tmp_path):
     lst = tmp_path / "list.txt"
     lst.write_text(f"{FIX}/sample_data.h5\n{FIX}/sample_data_2_gzip.h5\n")
@@ -88,7 +85,6 @@ def test_hdf5_data_layer_matches_reference_test(tmp_path):
         np.testing.assert_array_equal(data.nchw().reshape(-1).numpy(), np.arange(off, off + 5 * ds))
 
 
-@need_fixtures
 def test_hdf5_data_layer_shuffle_covers_rows(tmp_path):
     lst = tmp_path / "list.txt"
     lst.write_text(f"{FIX}/sample_data.h5\n")
@@ -171,7 +167,6 @@ def test_hdf5_weights_via_copy_trained_layers(tmp_path):
     assert torch.equal(a.net.flat_data, b.net.flat_data)
 
 
-@need_fixtures
 def test_train_from_hdf5_solver_data(tmp_path):
     """The reference's GradientBasedSolver fixture net (test_gradient_based_solver.cpp:
     HDF5Data over solver_data.h5 -> InnerProduct -> EuclideanLoss) trains end to end."""

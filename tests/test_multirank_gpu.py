@@ -30,7 +30,7 @@ def _env():
 
 @pytest.mark.timeout(300)
 def test_bench_two_ranks_share_gpu(gpu):
-    r = subprocess.run([sys.executable, "-u", "bench.py", "--gpus", "2", "--share-gpu", "--verify-average",
+    r = subprocess.run([sys.executable, "-u", "bench.py", "--gpus", "2", "--share-gpu", "--verify-average", "--full",
                         "--steps", "6", "--warmup", "3", "--tau", "3"], cwd=ROOT, env=_env(),
                        capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -70,7 +70,7 @@ def test_bench_eight_ranks_share_gpu(gpu):
     averaged masters on all 8 ranks, and the self-diagnosis block of the N > 1 JSON."""
     env = _env()
     env["OMP_NUM_THREADS"] = "2"
-    r = subprocess.run([sys.executable, "-u", "bench.py", "--gpus", "8", "--share-gpu", "--verify-average",
+    r = subprocess.run([sys.executable, "-u", "bench.py", "--gpus", "8", "--share-gpu", "--verify-average", "--full",
                         "--steps", "4", "--warmup", "2", "--tau", "2"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -10,8 +10,8 @@ import torch
 from sparknet_amd import dsl, proto
 from sparknet_amd.core.net import Net
 
-REF = "/root/reference/caffe"
-have_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
+# the reference's model definitions (prototxt settings files), stored with the tests
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "prototxt")
 
 
 def dsl_lenet(batch=4):
@@ -47,7 +47,6 @@ def test_dsl_lenet_structure_and_roundtrip():
     assert net.blob_by_name("ip2").shape == (4, 10)
 
 
-@have_ref
 @pytest.mark.parametrize("path", ["examples/cifar10/cifar10_quick_train_test.prototxt",
                                   "examples/cifar10/cifar10_full_train_test.prototxt",
                                   "models/bvlc_reference_caffenet/train_val.prototxt",
@@ -61,7 +60,6 @@ def test_reference_prototxt_roundtrip(path):
     assert b == n
 
 
-@have_ref
 def test_replace_data_layers_caffenet_and_solver():
     n = dsl.load_net_prototxt(os.path.join(REF, "models/bvlc_reference_caffenet/train_val.prototxt"))
     n = dsl.replace_data_layers(n, 4, 2, 3, 227, 227)
@@ -77,7 +75,6 @@ def test_replace_data_layers_caffenet_and_solver():
     assert sum(p.caffe_count for p in train.learnable_params) == 60965224
 
 
-@have_ref
 def test_zoo_matches_reference_prototxt_shapes():
     """DSL-built zoo models have exactly the reference models' parameter blobs."""
     from sparknet_amd import models

@@ -5,12 +5,12 @@ prototxt written for this repo — padding-layer folding (simple, a padding laye
 two-top data layer, a whole V0 CaffeNet), V0 -> V1 (simple, every parameter), the
 V0 -> V1 -> V2 chain, every V1 layer type instantiable after upgrade, and the solver type
 upgrade — plus the data-transformation upgrade (upgrade_proto.cpp:586-646) and a V0
-caffemodel loaded through ``Net.copy_trained_layers_from``.  When the reference tree is
-present, ``test_reference_fixtures`` additionally runs every string fixture of the
-reference test file through the matching upgrade function and compares the result
-(the fixtures are read as data; the reference code is not executed)."""
+caffemodel loaded through ``Net.copy_trained_layers_from``.  ``test_reference_fixtures``
+additionally runs every prototxt string pair of the reference test file (stored in
+tests/golden/upgrade_proto_cases.json) through the matching upgrade function and compares
+the result."""
+import json
 import os
-import re
 
 import pytest
 import torch
@@ -240,24 +240,16 @@ def test_v1_upgrade_param_specs_and_share_mode():
     assert [(p.lr_mult, p.decay_mult) for p in ps] == [(1.0, 1.0), (2.0, 0.0)]
 
 
-REF_TEST = "/root/reference/caffe/src/caffe/test/test_upgrade_proto.cpp"
+CASES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "upgrade_proto_cases.json")
 
 
 def _fixtures():
     """(runner, input text, expected text) for every RunPaddingUpgradeTest / RunV0UpgradeTest /
-    RunV1UpgradeTest call of the reference test file (string literals read as data)."""
-    src = open(REF_TEST).read()
-    out = []
-    for body in re.split(r"\nTEST_F\(", src)[1:]:
-        strings = {}
-        for m in re.finditer(r"const string& (\w+) =\s*((?:\"(?:[^\"\\]|\\.)*\"\s*)+);", body):
-            strings[m.group(1)] = "".join(re.findall(r"\"((?:[^\"\\]|\\.)*)\"", m.group(2)))
-        for m in re.finditer(r"this->(Run(?:Padding|V0|V1)UpgradeTest)\(\s*(\w+),\s*(\w+)\)", body):
-            out.append((m.group(1), strings[m.group(2)], strings[m.group(3)]))
-    return out
+    RunV1UpgradeTest call of the reference test file: the prototxt strings, stored as data."""
+    with open(CASES) as f:
+        return [(c["runner"], c["input"], c["expected"]) for c in json.load(f)]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TEST), reason="reference tree not present")
 def test_reference_fixtures():
     fx = _fixtures()
     assert len(fx) == 8  # 3 padding, V0 simple / all params / ImageNet, V1 simple / ImageNet, and one more V1
