@@ -237,12 +237,16 @@ class Solver:
         seg_of = {seg[0]: seg for seg in self.segments}
         final, late = {}, set()
         for li, layer in enumerate(net.layers):
+            # a Scale fused into its BatchNorm (engine.fuse_bn_scale_relu): the BatchNorm, an
+            # earlier layer, writes its gradients
+            writer = getattr(layer, "fused_into", None) if layer.params else None
+            wl = net.layers.index(writer) if writer is not None else li
             for i, p in enumerate(layer.params):
                 if p.offset not in seg_of:
                     continue
                 if not net.layer_need_backward[li] or not layer.param_grads_needed(i):
                     late.add(p.offset)
-                final[p.offset] = min(final.get(p.offset, li), li)
+                final[p.offset] = min(final.get(p.offset, wl), wl)
         groups: dict = {}
         for off, li in final.items():
             if off not in late:

@@ -165,6 +165,66 @@ def ConcatLayer(name, bottom, axis=1, top=None):
     return lp
 
 
+def BatchNormLayer(name, bottom, *, top=None, in_place=False, use_global_stats=None,
+                   moving_average_fraction=None, eps=None, param=None):
+    """``param`` defaults to the three lr_mult-0 specs every public BatchNorm prototxt spells out."""
+    lp = _base("BatchNorm", name, bottom, list(bottom) if in_place else top)
+    bp = lp.batch_norm_param
+    bp.SetInParent()
+    if use_global_stats is not None:
+        bp.use_global_stats = use_global_stats
+    if moving_average_fraction is not None:
+        bp.moving_average_fraction = moving_average_fraction
+    if eps is not None:
+        bp.eps = eps
+    _params(lp, [(0.0, 0.0)] * 3 if param is None else param)
+    return lp
+
+
+def ScaleLayer(name, bottom, *, top=None, in_place=False, axis=1, num_axes=1, filler=None, bias_term=False,
+               bias_filler=None, param=None):
+    lp = _base("Scale", name, bottom, list(bottom[:1]) if in_place else top)
+    sp = lp.scale_param
+    sp.SetInParent()
+    if axis != 1:
+        sp.axis = axis
+    if num_axes != 1:
+        sp.num_axes = num_axes
+    if filler is not None:
+        sp.filler.CopyFrom(_filler(filler))
+    if bias_term:
+        sp.bias_term = True
+    if bias_filler is not None:
+        sp.bias_filler.CopyFrom(_filler(bias_filler))
+    _params(lp, param)
+    return lp
+
+
+def BiasLayer(name, bottom, *, top=None, in_place=False, axis=1, num_axes=1, filler=None, param=None):
+    lp = _base("Bias", name, bottom, list(bottom[:1]) if in_place else top)
+    bp = lp.bias_param
+    bp.SetInParent()
+    if axis != 1:
+        bp.axis = axis
+    if num_axes != 1:
+        bp.num_axes = num_axes
+    if filler is not None:
+        bp.filler.CopyFrom(_filler(filler))
+    _params(lp, param)
+    return lp
+
+
+def EltwiseLayer(name, bottom, operation="SUM", *, coeff=None, top=None, stable_prod_grad=None):
+    lp = _base("Eltwise", name, bottom, top)
+    ep = lp.eltwise_param
+    ep.operation = {"PROD": 0, "SUM": 1, "MAX": 2}[operation.upper()] if isinstance(operation, str) else operation
+    if coeff:
+        ep.coeff.extend(float(c) for c in coeff)
+    if stable_prod_grad is not None:
+        ep.stable_prod_grad = stable_prod_grad
+    return lp
+
+
 def NetParam(name, *layers):
     net = proto.NetParameter(name=name)
     for lp in layers:
@@ -220,4 +280,8 @@ pooling_layer = PoolingLayer
 inner_product_layer = InnerProductLayer
 relu_layer = ReLULayer
 softmax_with_loss = SoftmaxWithLoss
+batch_norm_layer = BatchNormLayer
+scale_layer = ScaleLayer
+bias_layer = BiasLayer
+eltwise_layer = EltwiseLayer
 net_param = NetParam

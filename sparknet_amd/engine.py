@@ -52,12 +52,62 @@ def fuse_relu(net) -> int:
         prod.fuse_relu = True
         relu.fused = True
         n += 1
+    fuse_bn_scale_relu(net)
     fuse_relu_backward(net)
     fuse_dropout(net)
     fuse_concat(net)
     fuse_pool_lrn(net)
     fuse_lrn_pool_backward(net)
     batch_weight_flips(net)
+    return n
+
+
+def fuse_bn_scale_relu(net) -> int:
+    """Run BatchNorm -> Scale -> ReLU chains (every conv block of a Caffe ResNet) inside the
+    BatchNorm layer's kernels (csrc/kernels/bn_scale.hip): 3 passes over the activation forward
+    and 7 backward instead of the three layers' 8 and 14 (batch_norm_layer.cu, scale_layer.cu,
+    relu_layer.cu).  The pattern: a BatchNorm on a 4-D or 2-D blob, immediately followed by a
+    one-bottom per-channel Scale (axis 1, num_axes 1) in place on its top, optionally followed
+    by a slope-0 ReLU in place on the same blob.  gamma / beta stay the Scale layer's params
+    (flat-buffer offsets, names, multipliers and the .caffemodel layout are unchanged); the Scale
+    and ReLU layers become no-ops in both directions.  The three layers must agree on whether
+    they run backward.  GPU only, not with debug_info; returns the number of fused chains."""
+    net.bn_scale_fused = getattr(net, "bn_scale_fused", 0)  # chains fused so far, for reports and tests
+    if net.device.type != "cuda" or net.debug_info or not features.enabled("fuse_bn_scale"):
+        return 0
+    n = 0
+    for li in range(len(net.layers) - 1):
+        bn, sc = net.layers[li], net.layers[li + 1]
+        if bn.type_name != "BatchNorm" or sc.type_name != "Scale" or bn.fused_scale is not None:
+            continue
+        blob = net.top_ids[li][0]
+        if len(net.bottom_vecs[li][0].shape) not in (2, 4):
+            continue
+        if net.bottom_ids[li + 1] != [blob] or net.top_ids[li + 1] != [blob]:
+            continue  # two bottoms, not in place, or another blob
+        if sc.scale is None or (sc.axis, sc.k) != (1, 1) or sc.fused_into is not None:
+            continue
+        need = net.layer_need_backward[li]
+        if net.layer_need_backward[li + 1] != need or (need and not net.bottom_need_backward[li + 1][0]):
+            continue
+        relu = net.layers[li + 2] if li + 2 < len(net.layers) else None
+        if (relu is not None and relu.type_name == "ReLU" and getattr(relu, "slope", 1.0) == 0.0
+                and net.bottom_ids[li + 2] == [blob] and net.top_ids[li + 2] == [blob] and not relu.fused
+                and not relu.bwd_fused):
+            if net.layer_need_backward[li + 2] != need or (need and not net.bottom_need_backward[li + 2][0]):
+                continue
+            relu.fused = True      # forward: applied by the BatchNorm kernel
+            relu.bwd_fused = True  # backward: the BatchNorm kernels gate with the top
+            relu.bn_fused = True   # ... so fuse_relu_backward must not gate it in a consumer too
+            bn.fused_relu = True
+        bn.fused_scale = sc
+        sc.fused_into = bn
+        # BranchStreams: the BatchNorm backward writes the Scale layer's param gradients
+        ex = dict(getattr(bn, "sched_extra", None) or {})
+        ex["bwd_w"] = set(ex.get("bwd_w", ())) | {("p", p.offset) for p in sc.params}
+        bn.sched_extra = ex
+        n += 1
+    net.bn_scale_fused += n
     return n
 
 
@@ -317,7 +367,7 @@ def fuse_relu_backward(net) -> int:
     for li, relu in enumerate(net.layers):
         if relu.type_name != "ReLU" or getattr(relu, "slope", 1.0) != 0.0:
             continue
-        if net.bottom_ids[li] != net.top_ids[li]:
+        if net.bottom_ids[li] != net.top_ids[li] or getattr(relu, "bn_fused", False):
             continue
         blob = net.top_ids[li][0]
         consumers = [lj for lj in range(li + 1, len(net.layers)) if blob in net.bottom_ids[lj]]

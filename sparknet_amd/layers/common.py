@@ -1,8 +1,9 @@
 """Structural layers: Split, Concat, Slice, Eltwise, Flatten, Reshape, Silence, Tile,
-Reduction, ArgMax, BatchReindex, Filter, Embed, MVN, BatchNorm, SPP.
+Reduction, ArgMax, BatchReindex, Filter, Embed, MVN, BatchNorm, Scale, Bias, SPP.
 
 References: caffe/src/caffe/layers/{split,concat,slice,eltwise,flatten,reshape,silence,
-tile,reduction,argmax,batch_reindex,filter,embed,mvn,batch_norm,spp}_layer.*.
+tile,reduction,argmax,batch_reindex,filter,embed,mvn,batch_norm,spp}_layer.*; Scale and Bias
+follow upstream Caffe's scale_layer.cpp / bias_layer.cpp (newer than the reference snapshot).
 
 Channel-axis operations on 4-D blobs (Concat/Slice along axis 1) act on the physical
 last axis of the NHWC storage.  Flatten/Reshape keep Caffe's logical (C, H, W) order by
@@ -13,6 +14,8 @@ channel Concat, csrc/kernels/layers.hip for the rest, wrapped by ops.layers_hip)
 tensor-math bodies are the fp32 CPU reference path.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -49,6 +52,11 @@ def _to_logical(blob, diff=False):
     if blob.is_image:
         return _lh().nhwc_to_nchw(t)
     return t
+
+
+def _as(t, dtype):
+    """``t`` in ``dtype`` (a 2-D Input blob is fp32 next to bf16 activations): a HIP cast if needed."""
+    return t if t.dtype == dtype else _lh().cast(t, dtype)
 
 
 def _from_logical(t, blob):
@@ -848,9 +856,15 @@ class MVNLayer(Layer):
 @register("BatchNorm")
 class BatchNormLayer(Layer):
     """batch_norm_layer.cpp: normalisation only (no scale/shift), 3 param blobs
-    (running mean, running variance, moving-average factor) with lr_mult forced to 0."""
+    (running mean, running variance, moving-average factor) with lr_mult forced to 0.
+
+    ``fused_scale`` / ``fused_relu`` (engine.fuse_bn_scale_relu): the per-channel Scale and the
+    ReLU that follow in place on the top run inside this layer's kernels
+    (csrc/kernels/bn_scale.hip); gamma / beta stay the Scale layer's own params."""
     exact_bottoms = 1
     exact_tops = 1
+    fused_scale = None
+    fused_relu = False
 
     def layer_setup(self, bottoms, tops):
         p = self.lp.batch_norm_param
@@ -880,7 +894,42 @@ class BatchNormLayer(Layer):
         inner = x.numel() // (x.shape[0] * x.shape[1]) if x.dim() > 1 else 1
         return x.shape[0], x.shape[1] if x.dim() > 1 else 1, inner
 
+    def _forward_fused(self, bottoms, tops):
+        lh = _lh()
+        sc = self.fused_scale
+        x = _as(bottoms[0].data, tops[0].dtype)  # the kernels read and write one dtype: the top's
+        R, C_, _ = self._gpu_geom(x)
+        if self.use_global:
+            self.stats = (lh.BN_GLOBAL, self.mean.data, self.var.data, self.factor.data, self.eps)
+        else:
+            mean, _, inv = lh.bn_stats(x, R, C_, self.eps, (self.mean.data, self.var.data, self.factor.data),
+                                       self.frac, R / max(R - 1, 1))
+            self.stats = (lh.BN_BATCH, mean, inv, None, self.eps)
+        self.x = x  # xhat is recomputed from the input in backward, never stored
+        tops[0].data = lh.bn_fwd(x, R, C_, self.stats, sc.scale.data, sc.bias.data if sc.bias is not None else None,
+                                 self.fused_relu)
+
+    def _backward_fused(self, tops, propagate_down, bottoms):
+        lh = _lh()
+        sc = self.fused_scale
+        y, x = tops[0].data, self.x
+        dy = _as(tops[0].diff, y.dtype)
+        R, C_, _ = self._gpu_geom(x)
+        batch = self.stats[0] == lh.BN_BATCH
+        gflag = sc._flag(0) if sc.param_grads_needed(0) else lh.GRAD_SKIP
+        bflag = sc._flag(1) if sc.bias is not None and sc.param_grads_needed(1) else lh.GRAD_SKIP
+        pd = propagate_down[0]
+        coef = None
+        if gflag or bflag or (pd and batch):
+            coef = lh.bn_bwd_reduce(dy, x, y, R, C_, self.stats, self.fused_relu, sc.scale.diff, gflag,
+                                    sc.bias.diff if sc.bias is not None else None, bflag, want_coef=pd and batch)
+        if pd:
+            dx = lh.bn_bwd_dx(dy, x, y, R, C_, self.stats, self.fused_relu, sc.scale.data, coef)
+            bottoms[0].diff = _as(dx, bottoms[0].dtype)
+
     def forward(self, bottoms, tops):
+        if self.fused_scale is not None:
+            return self._forward_fused(bottoms, tops)
         if bottoms[0].data.is_cuda:
             lh = _lh()
             x = bottoms[0].data
@@ -916,6 +965,8 @@ class BatchNormLayer(Layer):
         tops[0].data = self.xhat.to(tops[0].dtype)
 
     def backward(self, tops, propagate_down, bottoms):
+        if self.fused_scale is not None:
+            return self._backward_fused(tops, propagate_down, bottoms)
         if not propagate_down[0]:
             return
         if tops[0].diff.is_cuda:
@@ -939,6 +990,289 @@ class BatchNormLayer(Layer):
             g = (dy - self._bc(dy.mean(dim=dims), dy) - xh * self._bc((dy * xh).mean(dim=dims), dy))
             g = g * self._bc(self.inv_std, dy)
         bottoms[0].diff = g.to(bottoms[0].dtype)
+
+
+class _BroadcastLayer(Layer):
+    """Shared body of Scale and Bias (scale_layer.cpp, bias_layer.cpp): ``y = x * s + b`` with
+    s / b of shape ``bottom[0].shape[axis : axis + num_axes]`` broadcast over the other axes.
+    The coefficient is a learned param (one bottom) or ``bottom[1]`` (two bottoms).
+
+    Layout.  4-D blobs are stored NHWC, so the covered axes form one ``[outer][A][inner]``
+    decomposition of the storage only when they are adjacent there (C, H, W, HW, N, CHW, NCHW,
+    scalar); a multi-axis param is then kept in storage order and ``to_caffe`` / ``from_caffe``
+    permute, as for the conv weights.  The other combinations — (N,C), (N,C,H), (C,H) — run on
+    an NCHW copy.  Non-4-D blobs are stored plain and always decompose.
+
+    GPU: ``inner == 1`` (per-channel, whole-shape, scalar) runs the vectorised per-channel
+    kernels of csrc/kernels/bn_scale.hip without normalisation; ``inner > 1`` a plain
+    broadcast kernel plus ``axis_reduce``."""
+    min_bottoms = 1
+    max_bottoms = 2
+    exact_tops = 1
+    supports_grad_overwrite = True
+    has_scale = True
+    fused_into = None  # the BatchNorm layer running this Scale (engine.fuse_bn_scale_relu)
+
+    # -- geometry ----------------------------------------------------------------------
+    def _axes(self, bottoms, axis, num_axes):
+        b0 = bottoms[0]
+        nd = len(b0.shape)
+        if len(bottoms) == 2:
+            k = len(bottoms[1].shape)
+            # a 0-axis bottom[1] is a scalar whatever the axis (scale_layer.cpp)
+            a = 0 if k == 0 else b0.canonical_axis(axis)
+        else:
+            a = b0.canonical_axis(axis)
+            if num_axes < -1:
+                raise ValueError(f"{self.type_name} {self.name!r}: num_axes must be >= -1")
+            k = nd - a if num_axes == -1 else num_axes
+        if not (0 <= a <= nd and a + k <= nd):
+            raise ValueError(f"{self.type_name} {self.name!r}: axes [{a}, {a + k}) outside bottom {b0.shape}")
+        if len(bottoms) == 2 and tuple(b0.shape[a:a + k]) != tuple(bottoms[1].shape):
+            raise ValueError(f"{self.type_name} {self.name!r}: bottom[1] shape {bottoms[1].shape} does not match "
+                             f"bottom[0] axes [{a}, {a + k}) of {b0.shape}")
+        return a, k
+
+    def _plan(self, bottoms):
+        """Sets ``cshape`` (Caffe-order coefficient shape), ``logical`` (outer, A, inner of the
+        NCHW order), ``phys`` (the same for the storage order, or None: NCHW-copy route) and
+        ``perm`` (covered axes in storage order, as indices into cshape)."""
+        b0 = bottoms[0]
+        a, k = self.axis, self.k
+        S = b0.shape
+        self.cshape = tuple(S[a:a + k])
+        self.logical = (b0.count_range(0, a), b0.count_range(a, a + k), b0.count_range(a + k))
+        self.perm = list(range(k))
+        # bottom[1] needs its NCHW order unless both blobs share the NHWC storage order
+        self.b1_logical = len(bottoms) == 2 and bottoms[1].is_image and not b0.is_image
+        if not b0.is_image or k == 0:
+            self.phys = self.logical if k else (b0.count, 1, 1)
+            return
+        pos = {0: 0, 1: 3, 2: 1, 3: 2}  # logical axis -> storage position
+        cov = sorted(range(a, a + k), key=lambda l: pos[l])
+        ps = [pos[l] for l in cov]
+        if ps != list(range(ps[0], ps[0] + k)):
+            self.phys = None
+            self.b1_logical = len(bottoms) == 2 and bottoms[1].is_image
+            return
+        self.perm = [l - a for l in cov]
+        if len(bottoms) == 2 and self.perm != list(range(k)) and not bottoms[1].is_image:
+            self.phys = None  # bottom[1] is stored in Caffe order
+            return
+        P = (S[0], S[2], S[3], S[1])
+        self.phys = (math.prod(P[:ps[0]]), self.logical[1], math.prod(P[ps[0] + k:]))
+
+    def _add_coef(self, filler, default):
+        from .. import proto
+        if filler is None:
+            filler = proto.FillerParameter(type="constant", value=default)
+        k, perm = self.k, self.perm
+        if perm == list(range(k)):
+            return self.add_param(self.cshape, filler=filler)
+        inv = [perm.index(i) for i in range(k)]
+        return self.add_param(self.cshape, tuple(self.cshape[i] for i in perm),
+                              to_caffe=lambda t: t.permute(inv).contiguous(),
+                              from_caffe=lambda t: t.permute(perm).contiguous(), filler=filler)
+
+    def reshape(self, bottoms, tops):
+        a, k = self._axes(bottoms, *self._axis_args)
+        if (a, k) != (self.axis, self.k) or tuple(bottoms[0].shape[a:a + k]) != self.cshape:
+            if self.params:
+                raise ValueError(f"{self.type_name} {self.name!r}: bottom reshaped under a learned coefficient")
+            self.axis, self.k = a, k
+        self._plan(bottoms)
+        tops[0].reshape(bottoms[0].shape, bottoms[0].dtype)
+
+    # -- CPU reference path (logical order, fp32) ----------------------------------------
+    def _bshape(self, b0):
+        return [1] * self.axis + list(self.cshape) + [1] * (len(b0.shape) - self.axis - self.k)
+
+    def _coef_cpu(self, p):
+        return p.to_caffe(p.data)
+
+    def _store_grad(self, i, g_caffe):
+        p = self.params[i]
+        g = p.from_caffe(g_caffe)
+        if self.grad_overwrite(i):
+            p.diff.copy_(g)
+        else:
+            p.diff.add_(g)
+
+    def _reduce_cpu(self, t):
+        o, A, i = self.logical
+        return t.reshape(o, A, i).sum(dim=(0, 2)).reshape(self.cshape)
+
+    @staticmethod
+    def _to_blob(t_logical, blob):
+        blob.data = (t_logical.permute(0, 2, 3, 1) if blob.is_image else t_logical).contiguous().to(blob.dtype)
+
+    def forward(self, bottoms, tops):
+        if self.fused_into is not None:
+            return
+        b0 = bottoms[0]
+        two = len(bottoms) == 2
+        if b0.data.is_cuda:
+            return self._forward_gpu(bottoms, tops)
+        x = b0.nchw().float()
+        bs = self._bshape(b0)
+        y = x
+        if self.has_scale:
+            s = (bottoms[1].nchw().float() if two else self._coef_cpu(self.scale)).reshape(bs)
+            self._x, self._s = x, s
+            y = y * s
+        if self.bias is not None:
+            y = y + self._coef_cpu(self.bias).reshape(bs)
+        elif not self.has_scale:
+            y = y + bottoms[1].nchw().float().reshape(bs)
+        self._to_blob(y, tops[0])
+
+    def backward(self, tops, propagate_down, bottoms):
+        if self.fused_into is not None:
+            return
+        two = len(bottoms) == 2
+        if tops[0].diff.is_cuda:
+            return self._backward_gpu(tops, propagate_down, bottoms)
+        dy = tops[0].nchw(diff=True).float()
+        if self.bias is not None:
+            bi = self.params.index(self.bias)
+            if self.param_grads_needed(bi):
+                self._store_grad(bi, self._reduce_cpu(dy))
+        dx = dy
+        if self.has_scale:
+            if (two and propagate_down[1]) or (not two and self.param_grads_needed(0)):
+                g = self._reduce_cpu(dy * self._x)
+                if two:
+                    b1 = bottoms[1]
+                    b1.diff = (g.permute(0, 2, 3, 1) if b1.is_image else g).contiguous().to(b1.dtype)
+                else:
+                    self._store_grad(0, g)
+            dx = dy * self._s
+        elif two and propagate_down[1]:
+            g = self._reduce_cpu(dy)
+            b1 = bottoms[1]
+            b1.diff = (g.permute(0, 2, 3, 1) if b1.is_image else g).contiguous().to(b1.dtype)
+        if propagate_down[0]:
+            b0 = bottoms[0]
+            b0.diff = (dx.permute(0, 2, 3, 1) if b0.is_image else dx).contiguous().to(b0.dtype)
+
+    # -- GPU path (HIP only) -------------------------------------------------------------
+    def _geom(self):
+        return self.phys if self.phys is not None else self.logical
+
+    def _vec_gpu(self, blob, diff=False):
+        """fp32 coefficient vector from bottom[1] in the order of the route in use."""
+        lh = _lh()
+        t = blob.diff if diff else blob.data
+        if self.b1_logical:
+            t = lh.nhwc_to_nchw(t)
+        return t.reshape(-1) if t.dtype == torch.float32 else lh.cast(t, torch.float32).reshape(-1)
+
+    def _grad_to_bottom1(self, g, b1):
+        lh = _lh()
+        g = g if b1.dtype == torch.float32 else lh.cast(g, b1.dtype)
+        if self.b1_logical:
+            b1.diff = _from_logical(g, b1)
+        else:
+            b1.diff = g.reshape(b1.data.shape)
+
+    def _apply_gpu(self, x, s, b):
+        """x * s + b over the route's [outer][A][inner]."""
+        lh = _lh()
+        o, A, i = self._geom()
+        if i == 1:
+            return lh.bn_fwd(x, o, A, lh.NO_STATS, s, b, False)
+        return lh.axis_scale_bias(x, s, b, A, i)
+
+    def _forward_gpu(self, bottoms, tops):
+        b0 = bottoms[0]
+        two = len(bottoms) == 2
+        x = _as(b0.data if self.phys is not None else _to_logical(b0), tops[0].dtype)
+        s = b = None
+        if self.has_scale:
+            s = self._vec_gpu(bottoms[1]) if two else self.scale.data.reshape(-1)
+            self._x, self._s = x, s  # the input stays alive for an in-place backward
+        if self.bias is not None:
+            b = self.bias.data.reshape(-1)
+        elif not self.has_scale:
+            b = self._vec_gpu(bottoms[1])
+        y = self._apply_gpu(x, s, b)
+        tops[0].data = y if self.phys is not None else _from_logical(y, tops[0])
+
+    def _sum_gpu(self, dy, x, out, flag):
+        """out (+)= sum over (outer, inner) of dy (* x); returns the fp32 vector."""
+        lh = _lh()
+        o, A, i = self._geom()
+        if out is None:
+            out = torch.empty(A, dtype=torch.float32, device=dy.device)
+            flag = lh.GRAD_STORE
+        out = out.view(-1)
+        if i == 1:
+            if x is not None:
+                lh.bn_bwd_reduce(dy, x, None, o, A, lh.NO_STATS, False, dgamma=out, gflag=flag, want_coef=False)
+            else:
+                lh.bn_bwd_reduce(dy, None, None, o, A, lh.NO_STATS, False, dbeta=out, bflag=flag, want_coef=False)
+        else:
+            lh.axis_reduce(lh.RED_DOT if x is not None else lh.RED_SUM, dy, x, 1, o, A, i, out=out,
+                           acc=flag == lh.GRAD_ACC)
+        return out
+
+    def _flag(self, i):
+        lh = _lh()
+        return lh.GRAD_STORE if self.grad_overwrite(i) else lh.GRAD_ACC
+
+    def _backward_gpu(self, tops, propagate_down, bottoms):
+        two = len(bottoms) == 2
+        dy = _as(tops[0].diff if self.phys is not None else _to_logical(tops[0], diff=True), tops[0].data.dtype)
+        if self.bias is not None:
+            bi = self.params.index(self.bias)
+            if self.param_grads_needed(bi):
+                self._sum_gpu(dy, None, self.bias.diff, self._flag(bi))
+        if self.has_scale:
+            if two and propagate_down[1]:
+                self._grad_to_bottom1(self._sum_gpu(dy, self._x, None, 0), bottoms[1])
+            elif not two and self.param_grads_needed(0):
+                self._sum_gpu(dy, self._x, self.scale.diff, self._flag(0))
+        elif two and propagate_down[1]:
+            self._grad_to_bottom1(self._sum_gpu(dy, None, None, 0), bottoms[1])
+        if propagate_down[0]:
+            if not self.has_scale:
+                bottoms[0].diff = _as(tops[0].diff, bottoms[0].dtype)
+                return
+            dx = _as(self._apply_gpu(dy, self._s, None), bottoms[0].dtype)
+            bottoms[0].diff = dx if self.phys is not None else _from_logical(dx, bottoms[0])
+
+
+@register("Scale")
+class ScaleLayer(_BroadcastLayer):
+    """scale_layer.cpp: params [scale, bias] with one bottom, [bias] with two (the blob order
+    of public .caffemodel files); default fillers constant 1 / constant 0."""
+
+    def layer_setup(self, bottoms, tops):
+        p = self.lp.scale_param
+        self._axis_args = (int(p.axis), int(p.num_axes))
+        self.axis, self.k = self._axes(bottoms, *self._axis_args)
+        self._plan(bottoms)
+        self.scale = self.bias = None
+        if len(bottoms) == 1:
+            self.scale = self._add_coef(p.filler if p.HasField("filler") else None, 1.0)
+        if p.bias_term:
+            self.bias = self._add_coef(p.bias_filler if p.HasField("bias_filler") else None, 0.0)
+
+
+@register("Bias")
+class BiasLayer(_BroadcastLayer):
+    """bias_layer.cpp: y = x + b; the bias is a learned param (default filler constant 0) or
+    bottom[1]."""
+    has_scale = False
+
+    def layer_setup(self, bottoms, tops):
+        p = self.lp.bias_param
+        self._axis_args = (int(p.axis), int(p.num_axes))
+        self.axis, self.k = self._axes(bottoms, *self._axis_args)
+        self._plan(bottoms)
+        self.scale = self.bias = None
+        if len(bottoms) == 1:
+            self.bias = self._add_coef(p.filler if p.HasField("filler") else None, 0.0)
 
 
 @register("SPP")

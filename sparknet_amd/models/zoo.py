@@ -7,6 +7,9 @@
 * ``alexnet``        — caffe/models/bvlc_alexnet/train_val.prototxt (LRN before pooling)
 * ``googlenet``      — caffe/models/bvlc_googlenet/train_val.prototxt (aux heads 0.3)
 * ``vgg16``          — not in the reference; authored here (BASELINE config #5)
+* ``resnet50``       — not in the reference; the public Caffe ResNet-50 layout (conv without bias ->
+  BatchNorm -> Scale -> ReLU blocks, Eltwise SUM shortcuts)
+* ``resnet_cifar``   — not in the reference; the 6n+2-layer CIFAR ResNet from the same constructors
 
 Each builder returns a NetParameter whose data entry points are SparkNet ``JavaData``
 layers (TRAIN and TEST variants, like ProtoLoader.replaceDataLayers), and each has a
@@ -15,8 +18,9 @@ matching ``*_solver`` with the reference hyper-parameters.
 from __future__ import annotations
 
 from .. import proto
-from ..dsl import (AccuracyLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, Include, InnerProductLayer,
-                   LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer, SoftmaxWithLoss)
+from ..dsl import (AccuracyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer, Include,
+                   InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer, ScaleLayer,
+                   SoftmaxWithLoss)
 
 WB = [(1.0, 1.0), (2.0, 0.0)]   # weight / bias lr & decay mults used by the ImageNet models
 W12 = [{"lr_mult": 1.0}, {"lr_mult": 2.0}]
@@ -237,6 +241,71 @@ def vgg16(train_batch=64, test_batch=50, crop=224, classes=1000):
     return NetParam("VGG_ILSVRC_16_layers", *L)
 
 
+MSRA = {"type": "msra"}
+W1 = [(1.0, 1.0)]
+
+
+def _conv_bn(L, name, bn, bottom, k, n, stride=1, pad=0, relu=True):
+    """Bias-free convolution -> in-place BatchNorm -> in-place Scale (with bias) [-> in-place
+    ReLU]: the chain engine.fuse_bn_scale_relu runs in one kernel family.  ``bn`` is the suffix
+    of the bn* / scale* layer names (public ResNet naming)."""
+    L += [ConvolutionLayer(name, [bottom], (k, k), n, stride=stride if stride != 1 else None, pad=pad or None,
+                           weight_filler=MSRA, param=W1, bias_term=False),
+          BatchNormLayer("bn" + bn, [name], in_place=True),
+          ScaleLayer("scale" + bn, [name], in_place=True, bias_term=True)]
+    if relu:
+        L.append(_relu(name + "_relu", name))
+    return name
+
+
+def _bottleneck(L, tag, bottom, width, stride, project):
+    """res{tag}: 1x1 (stride) -> 3x3 -> 1x1 (x4), summed with the input or its projection."""
+    short = bottom
+    if project:
+        short = _conv_bn(L, f"res{tag}_branch1", f"{tag}_branch1", bottom, 1, 4 * width, stride=stride, relu=False)
+    x = _conv_bn(L, f"res{tag}_branch2a", f"{tag}_branch2a", bottom, 1, width, stride=stride)
+    x = _conv_bn(L, f"res{tag}_branch2b", f"{tag}_branch2b", x, 3, width, pad=1)
+    x = _conv_bn(L, f"res{tag}_branch2c", f"{tag}_branch2c", x, 1, 4 * width, relu=False)
+    L += [EltwiseLayer(f"res{tag}", [short, x], "SUM"), _relu(f"res{tag}_relu", f"res{tag}")]
+    return f"res{tag}"
+
+
+def resnet50(train_batch=32, test_batch=50, crop=224, classes=1000):
+    """ResNet-50 in the layout of the public Caffe release (He et al., ResNet-50-deploy.prototxt):
+    not in the reference; 25 557 032 learnable elements besides the BatchNorm statistics."""
+    L = list(data_layers(train_batch, test_batch, 3, crop, crop))
+    x = _conv_bn(L, "conv1", "_conv1", "data", 7, 64, stride=2, pad=3)
+    L.append(_pool("pool1", x, 3, 2))
+    x = "pool1"
+    for stage, (width, reps) in enumerate(((64, 3), (128, 4), (256, 6), (512, 3)), 2):
+        for r in range(reps):
+            x = _bottleneck(L, f"{stage}{chr(ord('a') + r)}", x, width, 2 if (r == 0 and stage > 2) else 1, r == 0)
+    L += [PoolingLayer("pool5", [x], Pooling.Ave, global_pooling=True),
+          _ip(f"fc{classes}", "pool5", classes, MSRA, _c(0.0)), *_head(f"fc{classes}", top5=True)]
+    return NetParam("ResNet-50", *L)
+
+
+def resnet_cifar(n=3, train_batch=128, test_batch=100, classes=10):
+    """The 6n+2-layer CIFAR ResNet (He et al. 2015, section 4.2): 3x3 stem, three stages of n
+    basic blocks at 16 / 32 / 64 channels, projection shortcuts where the shape changes."""
+    L = list(data_layers(train_batch, test_batch, 3, 32, 32))
+    x = _conv_bn(L, "conv1", "_conv1", "data", 3, 16, pad=1)
+    for stage, width in enumerate((16, 32, 64), 2):
+        for r in range(n):
+            tag = f"{stage}{chr(ord('a') + r)}" if n <= 26 else f"{stage}_{r + 1}"
+            stride = 2 if (r == 0 and stage > 2) else 1
+            short = x
+            if stride != 1:
+                short = _conv_bn(L, f"res{tag}_branch1", f"{tag}_branch1", x, 1, width, stride=stride, relu=False)
+            y = _conv_bn(L, f"res{tag}_branch2a", f"{tag}_branch2a", x, 3, width, stride=stride, pad=1)
+            y = _conv_bn(L, f"res{tag}_branch2b", f"{tag}_branch2b", y, 3, width, pad=1, relu=False)
+            L += [EltwiseLayer(f"res{tag}", [short, y], "SUM"), _relu(f"res{tag}_relu", f"res{tag}")]
+            x = f"res{tag}"
+    L += [PoolingLayer("pool_global", [x], Pooling.Ave, global_pooling=True),
+          _ip("fc", "pool_global", classes, MSRA, _c(0.0), W12), *_head("fc")]
+    return NetParam(f"ResNet-{6 * n + 2}-CIFAR", *L)
+
+
 # --- solvers ------------------------------------------------------------------------------
 
 def _solver(net, **kw):
@@ -285,11 +354,22 @@ def vgg16_solver(net=None):
                    gamma=0.1, stepsize=100000, display=20, max_iter=370000, momentum=0.9, weight_decay=5e-4)
 
 
+def resnet50_solver(net=None):
+    return _solver(net or resnet50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
+                   gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
+
+
+def resnet_cifar_solver(net=None):
+    return _solver(net or resnet_cifar(), test_iter=[100], test_interval=1000, base_lr=0.1, lr_policy="multistep",
+                   gamma=0.1, stepvalue=[32000, 48000], display=100, max_iter=64000, momentum=0.9, weight_decay=1e-4)
+
+
 MODELS = {
     "lenet": (lenet, lenet_solver), "cifar10_quick": (cifar10_quick, cifar10_quick_solver),
     "cifar10_full": (cifar10_full, cifar10_full_solver), "caffenet": (caffenet, caffenet_solver),
     "alexnet": (alexnet, alexnet_solver), "googlenet": (googlenet, googlenet_solver),
-    "vgg16": (vgg16, vgg16_solver),
+    "vgg16": (vgg16, vgg16_solver), "resnet50": (resnet50, resnet50_solver),
+    "resnet_cifar": (resnet_cifar, resnet_cifar_solver),
 }
 
 

@@ -1,6 +1,7 @@
 """ctypes wrappers of ``csrc/kernels/layers.hip``: the non-hot Caffe layer families on the
 GPU (neurons, PReLU, Eltwise, BatchNorm / MVN, axis copies, layout changes, row gathers /
-scatter-adds, Reduction, ArgMax, Caffe-ordered Im2col, the loss family).
+scatter-adds, Reduction, ArgMax, Caffe-ordered Im2col, the loss family) and of
+``csrc/kernels/bn_scale.hip`` (fused BatchNorm -> Scale -> ReLU, per-channel Scale / Bias).
 
 Every function launches HIP kernels on torch's current stream (graph-capturable); torch is
 used only to allocate outputs.  Tensors must be contiguous bf16 or fp32 device tensors.
@@ -131,6 +132,84 @@ def bn_global(rm, rv, factor, eps):
     inv = torch.empty_like(mean)
     call("bn_global", rm, rv, factor, Cn, float(eps), mean, inv)
     return mean, inv
+
+
+# -- fused BatchNorm -> Scale -> ReLU, per-channel Scale / Bias (csrc/kernels/bn_scale.hip) ----
+# x / y / dy / dx: contiguous [R][C_] tensors of one dtype (bf16 or fp32); per-channel vectors fp32.
+# ``stats`` = (mode, a, b, factor, eps): BN_NONE (no normalisation), BN_BATCH (a = mean,
+# b = inv_std) or BN_GLOBAL (a / b / factor = the running blobs, scaled inside the kernels).
+BN_NONE, BN_BATCH, BN_GLOBAL = 0, 1, 2
+GRAD_SKIP, GRAD_STORE, GRAD_ACC = 0, 1, 2
+NO_STATS = (BN_NONE, None, None, None, 0.0)
+
+
+def _bn_part(t, R, C_):
+    k = _lib.kernels()
+    k.sn_bn_part_floats.restype = C.c_longlong
+    n = int(k.sn_bn_part_floats(C.c_longlong(R), C.c_longlong(C_), C.c_longlong(dt(t))))
+    if n <= 0:
+        raise ValueError(f"layers_hip: unsupported per-channel geometry R={R} C={C_}")
+    return torch.empty(n, dtype=torch.float32, device=t.device), n
+
+
+def bn_stats(x, R, C_, eps, running=None, frac=0.0, unbias=1.0):
+    """(mean, var, inv_std) of x over its rows in one read (Welford partials, fixed-order
+    merge); ``running`` = (mean, var, factor) blobs to update in the same finalize launch."""
+    x = _c(x)
+    part, n = _bn_part(x, R, C_)
+    mean = torch.empty(C_, dtype=torch.float32, device=x.device)
+    var = torch.empty_like(mean)
+    inv = torch.empty_like(mean)
+    rm, rv, rf = running if running is not None else (None, None, None)
+    call("bn_stats", x, dt(x), R, C_, part, n, float(eps), mean, var, inv, rm, rv, rf, float(frac), float(unbias))
+    return mean, var, inv
+
+
+def bn_fwd(x, R, C_, stats, gamma=None, beta=None, relu=False):
+    """y = relu?(gamma (x - mean) inv_std + beta), one launch."""
+    x = _c(x)
+    mode, a, b, f, eps = stats
+    y = torch.empty_like(x)
+    call("bn_fwd", x, y, dt(x), R, C_, a, b, f, float(eps), mode, gamma, beta, int(bool(relu)))
+    return y
+
+
+def bn_bwd_reduce(dy, x, y, R, C_, stats, relu, dgamma=None, gflag=GRAD_SKIP, dbeta=None, bflag=GRAD_SKIP,
+                  want_coef=True):
+    """Pass 1 of the backward: dbeta (+)= sum g, dgamma (+)= sum g xhat with g = dy [y > 0];
+    returns the [2][C_] coefficients of bn_bwd_dx (None unless ``want_coef``)."""
+    dy = _c(dy)
+    mode = stats[0]
+    need_x = gflag != GRAD_SKIP or mode == BN_BATCH
+    part, n = _bn_part(dy, R, C_)
+    coef = torch.empty(2 * C_, dtype=torch.float32, device=dy.device) if want_coef else None
+    call("bn_bwd_reduce", dy, _c(x) if need_x else None, _c(y) if relu else None, dt(dy), R, C_, stats[1], stats[2],
+         stats[3], float(stats[4]), mode, int(bool(relu)), int(need_x), part, n, dgamma, gflag, dbeta, bflag, coef)
+    return coef
+
+
+def bn_bwd_dx(dy, x, y, R, C_, stats, relu, gamma, coef):
+    """Pass 2: dx = gamma inv_std (g - sum g / M - xhat sum g xhat / M); without batch
+    statistics dx = g gamma inv_std."""
+    dy = _c(dy)
+    mode = stats[0]
+    dx = torch.empty_like(dy)
+    call("bn_bwd_dx", dy, _c(x) if mode == BN_BATCH else None, _c(y) if relu else None, dx, dt(dy), R, C_, stats[1],
+         stats[2], stats[3], float(stats[4]), mode, int(bool(relu)), gamma, coef)
+    return dx
+
+
+def axis_scale_bias(x, s, b, A, inner):
+    """y = x * s[a] + b[a] over [outer][A][inner] (s / b fp32 vectors, either may be None)."""
+    x = _c(x)
+    y = torch.empty_like(x)
+    call("axis_scale_bias", x, y, x.numel(), A, inner, s, b, dt(x))
+    return y
+
+
+def cast(x, dtype):
+    """Copy of x in another supported dtype."""
+    return neuron_fwd("Power", x, dtype, 1.0, 1.0, 0.0)
 
 
 # -- eltwise -------------------------------------------------------------------------------

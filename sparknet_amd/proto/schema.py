@@ -99,7 +99,8 @@ MESSAGES: dict[str, tuple[dict, list]] = {
         r("exclude", 9, "NetStateRule"),
         o("transform_param", 100, "TransformationParameter"), o("loss_param", 101, "LossParameter"),
         o("accuracy_param", 102, "AccuracyParameter"), o("argmax_param", 103, "ArgMaxParameter"),
-        o("batch_norm_param", 139, "BatchNormParameter"), o("concat_param", 104, "ConcatParameter"),
+        o("batch_norm_param", 139, "BatchNormParameter"), o("bias_param", 141, "BiasParameter"),
+        o("scale_param", 142, "ScaleParameter"), o("concat_param", 104, "ConcatParameter"),
         o("contrastive_loss_param", 105, "ContrastiveLossParameter"),
         o("convolution_param", 106, "ConvolutionParameter"), o("data_param", 107, "DataParameter"),
         o("dropout_param", 108, "DropoutParameter"), o("dummy_data_param", 109, "DummyDataParameter"),
@@ -131,6 +132,11 @@ MESSAGES: dict[str, tuple[dict, list]] = {
     "ConcatParameter": ({}, [o("axis", 2, "int32", 1), o("concat_dim", 1, "uint32", 1)]),
     "BatchNormParameter": ({}, [o("use_global_stats", 1, "bool"),
                                 o("moving_average_fraction", 2, "float", 0.999), o("eps", 3, "float", 1e-5)]),
+    "BiasParameter": ({}, [o("axis", 1, "int32", 1), o("num_axes", 2, "int32", 1),
+                           o("filler", 3, "FillerParameter")]),
+    "ScaleParameter": ({}, [o("axis", 1, "int32", 1), o("num_axes", 2, "int32", 1),
+                            o("filler", 3, "FillerParameter"), o("bias_term", 4, "bool", False),
+                            o("bias_filler", 5, "FillerParameter")]),
     "ContrastiveLossParameter": ({}, [o("margin", 1, "float", 1.0), o("legacy_version", 2, "bool", False)]),
     "ConvolutionParameter": ({"Engine": ENGINE}, [
         o("num_output", 1, "uint32"), o("bias_term", 2, "bool", True), r("pad", 3, "uint32"),

@@ -20,6 +20,7 @@ DEFAULTS = {
     "zero_copy_concat": True,   # producers write straight into the Concat top
     "fuse_dropout": True,       # Dropout forward in the InnerProduct epilogue
     "fuse_fp8_quant": True,     # fp8 quantisation in the producing GEMM's epilogue
+    "fuse_bn_scale": True,      # BatchNorm -> Scale -> ReLU chains in the fused per-channel kernels
     "branch_depfree": True,     # dependency-free backward nodes on the least recently used stream
     "fuse_splitk": False,       # solver update sums split-K slabs (measured slower, opt-in)
     # convolution kernel selection (ops/hip.py)
