@@ -142,7 +142,10 @@ extern "C" int sn_softmax_bwd(const bf16_t* dy, const bf16_t* y, bf16_t* dx, lon
   return SN_CHECK_LAUNCH();
 }
 
-// top-k accuracy: hit if fewer than k classes score strictly higher than the label
+// top-k accuracy: hit if fewer than k classes rank ahead of the label in the reference's
+// descending sort of (score, class index) pairs (accuracy_layer.cpp: partial_sort with
+// std::greater<pair>): a strictly higher score, or a score that does not compare below the
+// label's (a tie; NaN against NaN) at a higher class index.
 __global__ void accuracy_rows(const bf16_t* __restrict__ x, const float* __restrict__ labels, float* __restrict__ hit,
                               float* __restrict__ valid, int M, int C, int k, int has_ignore, int ignore_label) {
   const int lane = threadIdx.x & 63;
@@ -150,9 +153,13 @@ __global__ void accuracy_rows(const bf16_t* __restrict__ x, const float* __restr
   if (row >= M) return;
   const int lab = (int)labels[row];
   const bf16_t* xr = x + (long long)row * C;
-  const float ls = bf2f(xr[min(max(lab, 0), C - 1)]);
+  const int lc = min(max(lab, 0), C - 1);
+  const float ls = bf2f(xr[lc]);
   float cnt = 0.f;
-  for (int c = lane; c < C; c += 64) cnt += bf2f(xr[c]) > ls ? 1.f : 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float v = bf2f(xr[c]);
+    cnt += (v > ls || (!(ls > v) && c > lc)) ? 1.f : 0.f;
+  }
   cnt = wave_sum(cnt);
   if (lane == 0) {
     bool v = !(has_ignore && lab == ignore_label);

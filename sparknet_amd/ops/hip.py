@@ -1124,7 +1124,7 @@ def sum_bf16(tensors, out=None):
 # --------------------------------------------------------------------------------------
 
 def softmax_loss_forward(x2, labels, ignore_label=None, normalize=True, outer_num=None):
-    x2 = _c(x2)
+    x2 = as_bf16(x2)
     M, Cn = x2.shape
     dev = x2.device
     prob = torch.empty((M, Cn), dtype=torch.float32, device=dev)
@@ -1161,7 +1161,7 @@ def softmax_backward(dy2, y2):
 
 
 def accuracy(x2, labels, top_k=1, ignore_label=None):
-    x2 = _c(x2)
+    x2 = as_bf16(x2)
     M, Cn = x2.shape
     rows = torch.empty((2, M), dtype=torch.float32, device=x2.device)
     out = torch.empty(2, dtype=torch.float32, device=x2.device)

@@ -371,10 +371,15 @@ def softmax_loss_backward(prob, labels, loss_weight, norm, ignore_label=None, dt
 def accuracy(x2, labels, top_k=1, ignore_label=None):
     lab = labels.reshape(-1).long()
     xf = x2.float()
-    # Caffe counts a hit when fewer than top_k classes score strictly higher.
-    lab_score = xf.gather(1, lab.clamp(0, xf.shape[1] - 1)[:, None])
-    higher = (xf > lab_score).sum(1)
-    hit = (higher < top_k).float()
+    # accuracy_layer.cpp sorts (score, class index) pairs in descending order and looks for the
+    # label among the first top_k: a class ranks ahead of the label when it scores strictly
+    # higher, or when it does not compare below the label's score (a tie; NaN against NaN)
+    # and has the higher index.
+    lc = lab.clamp(0, xf.shape[1] - 1)[:, None]
+    lab_score = xf.gather(1, lc)
+    idx = torch.arange(xf.shape[1], device=xf.device)[None, :]
+    ahead = (xf > lab_score) | (~(lab_score > xf) & (idx > lc))
+    hit = (ahead.sum(1) < top_k).float()
     valid = torch.ones_like(hit, dtype=torch.bool)
     if ignore_label is not None:
         valid = lab != ignore_label
