@@ -297,7 +297,8 @@ __global__ void im2col_nhwc(const bf16_t* __restrict__ x, bf16_t* __restrict__ c
 }
 
 // dx[n,h,w,coff+c] = sum over (p,q,r,s) mapping to (h,w) of dcol[(n,p,q)][(r,s,c)]  (gather)
-__global__ void col2im_nhwc(const bf16_t* __restrict__ dcol, bf16_t* __restrict__ dx, ConvG g) {
+// dcol is fp32: the per-tap terms are summed unrounded and dx is the one rounding to bf16
+__global__ void col2im_nhwc(const float* __restrict__ dcol, bf16_t* __restrict__ dx, ConvG g) {
   const long long total = (long long)g.N * g.H * g.W * g.Cg;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int c = (int)(i % g.Cg);
@@ -314,7 +315,7 @@ __global__ void col2im_nhwc(const bf16_t* __restrict__ dcol, bf16_t* __restrict_
         if (ww < 0 || ww % g.sw) continue;
         int q = ww / g.sw;
         if (q >= g.Q) continue;
-        acc += bf2f(dcol[(((long long)n * g.P + p) * g.Q + q) * g.Kpad + (r * g.S + s) * g.Cg + c]);
+        acc += dcol[(((long long)n * g.P + p) * g.Q + q) * g.Kpad + (r * g.S + s) * g.Cg + c];
       }
     }
     dx[pix * g.C + g.coff + c] = f2bf(acc);
@@ -341,7 +342,7 @@ extern "C" int sn_im2col(const bf16_t* x, bf16_t* col, long long N, long long H,
   return SN_CHECK_LAUNCH();
 }
 
-extern "C" int sn_col2im(const bf16_t* dcol, bf16_t* dx, long long N, long long H, long long W, long long C,
+extern "C" int sn_col2im(const float* dcol, bf16_t* dx, long long N, long long H, long long W, long long C,
                          long long P, long long Q, long long R, long long S, long long sh, long long sw, long long ph,
                          long long pw, long long dh, long long dw, long long Cg, long long Kpad, long long coff,
                          hipStream_t st) {

@@ -10,6 +10,8 @@
 * ``resnet50``       — not in the reference; the public Caffe ResNet-50 layout (conv without bias ->
   BatchNorm -> Scale -> ReLU blocks, Eltwise SUM shortcuts)
 * ``resnet_cifar``   — not in the reference; the 6n+2-layer CIFAR ResNet from the same constructors
+* ``mobilenet``      — not in the reference; the public Caffe MobileNet v1 layout (depthwise 3x3 +
+  pointwise 1x1 blocks, each conv followed by BatchNorm -> Scale -> ReLU)
 
 Each builder returns a NetParameter whose data entry points are SparkNet ``JavaData``
 layers (TRAIN and TEST variants, like ProtoLoader.replaceDataLayers), and each has a
@@ -245,16 +247,18 @@ MSRA = {"type": "msra"}
 W1 = [(1.0, 1.0)]
 
 
-def _conv_bn(L, name, bn, bottom, k, n, stride=1, pad=0, relu=True):
+def _conv_bn(L, name, bn, bottom, k, n, stride=1, pad=0, relu=True, group=1, names=None):
     """Bias-free convolution -> in-place BatchNorm -> in-place Scale (with bias) [-> in-place
     ReLU]: the chain engine.fuse_bn_scale_relu runs in one kernel family.  ``bn`` is the suffix
-    of the bn* / scale* layer names (public ResNet naming)."""
+    of the bn* / scale* layer names (public ResNet naming); ``names`` = (BatchNorm, Scale, ReLU)
+    layer names for models that name them differently."""
+    bn_name, scale_name, relu_name = names or ("bn" + bn, "scale" + bn, name + "_relu")
     L += [ConvolutionLayer(name, [bottom], (k, k), n, stride=stride if stride != 1 else None, pad=pad or None,
-                           weight_filler=MSRA, param=W1, bias_term=False),
-          BatchNormLayer("bn" + bn, [name], in_place=True),
-          ScaleLayer("scale" + bn, [name], in_place=True, bias_term=True)]
+                           group=group, weight_filler=MSRA, param=W1, bias_term=False),
+          BatchNormLayer(bn_name, [name], in_place=True),
+          ScaleLayer(scale_name, [name], in_place=True, bias_term=True)]
     if relu:
-        L.append(_relu(name + "_relu", name))
+        L.append(_relu(relu_name, name))
     return name
 
 
@@ -304,6 +308,38 @@ def resnet_cifar(n=3, train_batch=128, test_batch=100, classes=10):
     L += [PoolingLayer("pool_global", [x], Pooling.Ave, global_pooling=True),
           _ip("fc", "pool_global", classes, MSRA, _c(0.0), W12), *_head("fc")]
     return NetParam(f"ResNet-{6 * n + 2}-CIFAR", *L)
+
+
+# (tag, output width, stride of the depthwise 3x3) of MobileNet v1's 13 depthwise-separable blocks
+MOBILENET = (("2_1", 64, 1), ("2_2", 128, 2), ("3_1", 128, 1), ("3_2", 256, 2), ("4_1", 256, 1), ("4_2", 512, 2),
+             ("5_1", 512, 1), ("5_2", 512, 1), ("5_3", 512, 1), ("5_4", 512, 1), ("5_5", 512, 1), ("5_6", 1024, 2),
+             ("6", 1024, 1))
+
+
+def mobilenet(train_batch=32, test_batch=50, crop=224, classes=1000, alpha=1.0):
+    """MobileNet v1 (Howard et al. 2017) in the layout and layer names of the public Caffe
+    release: not in the reference.  3x3 / 2 stem, 13 blocks of depthwise 3x3 (``convX/dw``,
+    group == channels: csrc/kernels/conv_dw.hip) and pointwise 1x1 (``convX/sep``), each conv
+    bias-free with in-place BatchNorm -> Scale -> ReLU, global average ``pool6`` (any crop) and
+    ``fc7`` as a 1x1 convolution with bias.  4 231 976 learnable elements besides the BatchNorm
+    statistics at alpha = 1.  ``alpha`` is the paper's width multiplier; widths stay multiples
+    of 8 (the 16-byte channel lanes of the kernels)."""
+    def width(n):
+        return max(8, int(n * alpha + 4) // 8 * 8)
+
+    def block(name, tag, bottom, k, n, **kw):
+        return _conv_bn(L, name, None, bottom, k, n, names=(name + "/bn", name + "/scale", "relu" + tag), **kw)
+
+    L = list(data_layers(train_batch, test_batch, 3, crop, crop))
+    x = block("conv1", "1", "data", 3, width(32), stride=2, pad=1)
+    c = width(32)
+    for tag, n, stride in MOBILENET:
+        x = block(f"conv{tag}/dw", f"{tag}/dw", x, 3, c, stride=stride, pad=1, group=c)
+        c = width(n)
+        x = block(f"conv{tag}/sep", f"{tag}/sep", x, 1, c)
+    L += [PoolingLayer("pool6", [x], Pooling.Ave, global_pooling=True),
+          _conv("fc7", "pool6", 1, classes, wf=MSRA, bf=_c(0.0)), *_head("fc7", top5=True)]
+    return NetParam("MobileNet", *L)
 
 
 # --- solvers ------------------------------------------------------------------------------
@@ -364,12 +400,17 @@ def resnet_cifar_solver(net=None):
                    gamma=0.1, stepvalue=[32000, 48000], display=100, max_iter=64000, momentum=0.9, weight_decay=1e-4)
 
 
+def mobilenet_solver(net=None):
+    return _solver(net or mobilenet(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="poly", power=1.0,
+                   display=20, max_iter=500000, momentum=0.9, weight_decay=4e-5)
+
+
 MODELS = {
     "lenet": (lenet, lenet_solver), "cifar10_quick": (cifar10_quick, cifar10_quick_solver),
     "cifar10_full": (cifar10_full, cifar10_full_solver), "caffenet": (caffenet, caffenet_solver),
     "alexnet": (alexnet, alexnet_solver), "googlenet": (googlenet, googlenet_solver),
     "vgg16": (vgg16, vgg16_solver), "resnet50": (resnet50, resnet50_solver),
-    "resnet_cifar": (resnet_cifar, resnet_cifar_solver),
+    "resnet_cifar": (resnet_cifar, resnet_cifar_solver), "mobilenet": (mobilenet, mobilenet_solver),
 }
 
 

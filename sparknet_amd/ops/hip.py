@@ -222,6 +222,9 @@ def _conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=No
             call("conv3x3_direct", x, wc[j:j + 96], b[j:j + 96] if b is not None else None, None, y[..., j:],
                  s.N, s.H, s.W, s.C, 96, s.ph, int(relu), s.K)
         return y
+    if direct_io and ldy == s.K and depthwise_ok(s) and _dw_io_ok(x, w, y):
+        call("conv_dw_fwd", x, w, b, y, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw, int(relu))
+        return y
     if _implicit_ok(s):
         kred = s.R * s.S * s.Cg
         g = _geom(s)
@@ -343,6 +346,29 @@ _DIRECT_FP8 = features.enabled("conv_direct_fp8")
 
 def direct_fp8_ok(s: ConvSpec) -> bool:
     return _DIRECT_FP8 and direct_c64_ok(s)
+
+
+def depthwise_ok(s: ConvSpec) -> bool:
+    """Depthwise 3x3 convolutions the per-channel kernels take (csrc/kernels/conv_dw.hip): one
+    filter per channel (groups == C == K), whole 8-channel lanes, any stride and pad, no
+    dilation.  Everything else — a channel multiplier, other windows, C % 8 != 0 — keeps the
+    per-group path.  The switch is read on every call (SN_FEATURES=conv_depthwise=0)."""
+    return (s.groups == s.C == s.K and s.C % 8 == 0 and s.R == 3 and s.S == 3 and s.dh == 1 and s.dw == 1
+            and features.enabled("conv_depthwise"))
+
+
+def _dw_io_ok(*tensors) -> bool:
+    """The depthwise kernels read and write whole 16-byte lanes of dense bf16 tensors."""
+    return all(t is None or (t.dtype == BF16 and t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
+
+
+def _dw_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
+    k = _lib.kernels()
+    k.sn_conv_dw_part_floats.restype = C.c_longlong
+    n = int(k.sn_conv_dw_part_floats(*(C.c_longlong(v) for v in (s.N, s.P, s.Q, s.C))))
+    if n <= 0:
+        raise ValueError(f"depthwise weight gradient: unsupported geometry {s}")
+    return torch.empty(n, dtype=torch.float32, device=device), n
 
 
 def _side_covers(t: torch.Tensor) -> bool:
@@ -494,6 +520,13 @@ def _conv_backward(dy, x, w, s: ConvSpec, need_dx: bool, dw=None, db=None, gate=
 
 def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, ldd=0, ldx=0):
     ldd, ldx = ldd or s.K, ldx or s.C
+    if ((dw is not None or db is not None) and plan is None and ldd == s.K and ldx == s.C and depthwise_ok(s)
+            and _dw_io_ok(dy2, x) and not _dy_fp8_only(ws)):
+        # tap sums and the bias gradient in one pass over dy and x, slab partials, fixed-order finalize
+        part, n = _dw_part(s, x.device)
+        call("conv_dw_wgrad", dy2, x, part, n, dw, 0 if dw is None else 1 + int(dw_acc),
+             db, 0 if db is None else 1 + int(db_acc), s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
+        return
     if db is not None and not fused_db:
         assert ldd == s.K
         colsum(dy2, db, accumulate=db_acc)
@@ -665,6 +698,10 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, ldd=0, ldx=0, dx_out=None):
         gemm(s.N * s.H * s.W, s.Cg, kr2, A, B, dx, ldo, epi=EPI_BF16, groups=s.groups, c_gstride=s.Cg,
              gate=gate)
         return dx
+    if (ldd == s.K and depthwise_ok(s) and _dw_io_ok(dy, w, dx, gate) and not _side_covers(dx)
+            and not _dy_fp8_only(ws)):
+        call("conv_dw_dgrad", dy, w, gate, dx, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
+        return dx
     # generic: dcol = dy_g @ W_g, then col2im (gather, no atomics)
     assert ldd == s.K
     dy2 = dy.view(M, s.K)
@@ -676,8 +713,10 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, ldd=0, ldx=0, dx_out=None):
         wg = wp[g * s.Kg:(g + 1) * s.Kg]
         if kgp != s.Kg:
             wg = torch.cat([wg, torch.zeros((kgp - s.Kg, kpad), dtype=BF16, device=x.device)])
-        dcol = torch.empty((M, kpad), dtype=BF16, device=x.device)
-        gemm(M, kpad, kgp, Dense(dyg, dyg.stride(0), True), Dense(_c(wg), kpad, False), dcol, kpad, epi=EPI_BF16)
+        # dcol stays fp32: col2im sums up to R * S of its entries per input pixel, and rounding each
+        # to bf16 first costs 2^-8 of every term where the taps cancel, not 2^-8 of dx
+        dcol = torch.empty((M, kpad), dtype=torch.float32, device=x.device)
+        gemm(M, kpad, kgp, Dense(dyg, dyg.stride(0), True), Dense(_c(wg), kpad, False), dcol, kpad, epi=EPI_F32)
         call("col2im", dcol, dx, s.N, s.H, s.W, s.C, s.P, s.Q, s.R, s.S, s.sh, s.sw, s.ph, s.pw, s.dh, s.dw,
              s.Cg, kpad, g * s.Cg)
     if gate is not None:
