@@ -42,8 +42,8 @@ hip._DIRECT_FP8 = False
 res["fwd fp8 gemm"] = timed(lambda: hip.conv_forward_fp8(xq, wq, b, s, sc.deq(0), sc.deq(1), relu=True))
 hip._DIRECT_FP8 = True
 res["dgrad bf16 direct"] = timed(lambda: hip.conv_backward(dy, x, w, s, True, gate=x))
-ws = {"fp8_dgrad": (sc, 2, 3)}
-res["dgrad fp8 direct (+dy quant, flip)"] = timed(lambda: hip.conv_backward(dy, x, w, s, True, gate=x, ws=dict(ws)))
+ws = hip.ConvScratch(fp8_dgrad=hip.Fp8Dgrad(sc, 2, 3))
+res["dgrad fp8 direct (+dy quant, flip)"] = timed(lambda: hip.conv_backward(dy, x, w, s, True, gate=x, ws=ws))
 res["quant_fp8 of x"] = timed(lambda: hip.quant_fp8(x, sc.slot(0)))
 for k, v in res.items():
     print(f"{k:36s} {v:9.1f} us  {fl / v / 1e6:7.0f} TF/s")

@@ -972,10 +972,12 @@ def release_activations(net) -> int:
         blob._data = None
         blob._diff = None
         n += 1
+    from .ops.hip import ConvScratch
     for layer in net.layers:
-        for d in getattr(layer, "_ws", None) or ():
-            if isinstance(d, dict):
-                d.clear()
+        ws = getattr(layer, "_ws", None)
+        for d in ws if isinstance(ws, list) else ():
+            if isinstance(d, ConvScratch):  # the folded input kept from the forward, the fp8 copies of x and dy
+                d.release()
     gc.collect()
     torch.cuda.empty_cache()
     return n

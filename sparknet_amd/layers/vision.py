@@ -278,7 +278,8 @@ class ConvolutionLayer(Layer):
     def forward(self, bottoms, tops):
         w = self.weight.compute
         bias = self.bias.data if self.bias is not None else None
-        self._ws = [{} for _ in bottoms]  # forward -> backward scratch (e.g. folded input)
+        from ..ops.hip import ConvScratch
+        self._ws = [ConvScratch() for _ in bottoms]  # forward -> backward scratch (e.g. folded input)
         for i, (b, t) in enumerate(zip(bottoms, tops)):
             s = self.spec(b)
             side = self._fp8_out_side(s) if i == 0 else None
@@ -372,25 +373,22 @@ class ConvolutionLayer(Layer):
         w = self.weight.compute
         dw = self.weight.diff if self.param_grads_needed(0) else None
         db = self.bias.diff if (self.bias is not None and self.param_grads_needed(1)) else None
+        from ..ops.hip import ConvScratch, Fp8Dgrad, Fp8Wgrad
         for i, (t, b) in enumerate(zip(tops, bottoms)):
             s = self.spec(b)
             gate = b.data if self.relu_gate else None
-            ws = self._ws[i] if i < len(getattr(self, "_ws", ())) else None
-            if self.flipped_weights is not None:  # flipped for the whole net (engine.batch_weight_flips)
-                ws = {} if ws is None else ws
-                ws["wt"] = self.flipped_weights
+            ws = self._ws[i] if i < len(getattr(self, "_ws", ())) else ConvScratch()
+            ws.wt = self.flipped_weights  # flipped for the whole net (engine.batch_weight_flips), or None
             if self.fp8_dgrad_slots is not None and t.diff.is_cuda:  # e4m3 data gradient (engine.enable_fp8)
-                ws = {} if ws is None else ws
                 dy_side, self._fp8_dy_side = self._fp8_dy_side, None
-                ws["fp8_dgrad"] = (self.ctx.fp8, *self.fp8_dgrad_slots, dy_side)
+                ws.fp8_dgrad = Fp8Dgrad(self.ctx.fp8, *self.fp8_dgrad_slots, dy_side)
                 xq, self._fp8_xq = self._fp8_xq, None
                 if self.fp8_wgrad and xq is not None and dw is not None and i == 0:
-                    ws["fp8_wgrad"] = (self.ctx.fp8, self.fp8_slots[0], xq, self.fp8_dgrad_slots[0])
+                    ws.fp8_wgrad = Fp8Wgrad(self.ctx.fp8, self.fp8_slots[0], xq, self.fp8_dgrad_slots[0])
             if i == 0 and self.fp8_dx_out is not None and propagate_down[i] and self._fp8_ready():
-                ws = {} if ws is None else ws
                 prod, idy = self.fp8_dx_out
-                ws["fp8_dx_side"] = (self.ctx.fp8.slot(idy), self.ctx.fp8.is_e5m2(idy),
-                                     self._side_part("bwd", t.diff.device))
+                ws.fp8_dx_side = (self.ctx.fp8.slot(idy), self.ctx.fp8.is_e5m2(idy),
+                                  self._side_part("bwd", t.diff.device))
             dw_acc = not (dw is not None and self.grad_overwrite(0))
             db_acc = not (db is not None and self.grad_overwrite(1))
             sink = getattr(self, "slab_grad", None)
@@ -407,8 +405,9 @@ class ConvolutionLayer(Layer):
                     sink.end()  # this pass's gradient went to the flat buffer
                 dx = ops.conv_backward(t.diff, b.data, w, s, bool(propagate_down[i]), dw, db, gate, ws,
                                        dw_acc=dw_acc, db_acc=db_acc)
-            if ws is not None and "fp8_dx_side_out" in ws:
-                self.fp8_dx_out[0]._fp8_dy_side = ws.pop("fp8_dx_side_out")
+            side, ws.fp8_dx_side_out = ws.fp8_dx_side_out, None
+            if side is not None:
+                self.fp8_dx_out[0]._fp8_dy_side = side
             if propagate_down[i]:
                 b.diff = dx
 

@@ -11,13 +11,14 @@ import contextlib
 import ctypes as C
 import dataclasses
 import os
+from typing import NamedTuple
 
 import torch
 
 from . import _lib
 from ..utils import features
-from .gemm import (EPI_BF16, EPI_F32, EPI_F32_ACC, ConvGeom, Dense, FlipW, Im2col, colsum, gemm,
-                   linear_dgrad, linear_fwd, linear_wgrad)
+from .gemm import (EPI_BF16, EPI_F32, EPI_F32_ACC, ConvGeom, Dense, FlipW, Fp8Side, Im2col, colsum, fp8_side_output,
+                   gemm, linear_dgrad, linear_fwd, linear_wgrad, side_bytes)
 from .spec import POOL_MAX, ConvNdSpec, ConvSpec, PoolSpec
 
 call = _lib.call
@@ -72,6 +73,29 @@ def _implicit_ok(s: ConvSpec) -> bool:
     return s.Cg % 8 == 0 and s.C % 8 == 0
 
 
+def _unit_conv(s: ConvSpec) -> bool:  # stride 1, no dilation
+    return s.sh == 1 and s.sw == 1 and s.dh == 1 and s.dw == 1
+
+
+def _wgrad_implicit_ok(s: ConvSpec) -> bool:  # the weight gradient as an implicit GEMM: whole 8-channel chunks
+    return _implicit_ok(s) and s.Kg % 8 == 0
+
+
+def _dgrad_flip_geom_ok(s: ConvSpec) -> bool:
+    """The data gradient can run as a forward conv of dy over flip-transposed weights."""
+    return _unit_conv(s) and _wgrad_implicit_ok(s)
+
+
+def _plain_window(s: ConvSpec, r: int, p: int) -> bool:
+    """Ungrouped, stride-1, undilated r x r window with pad p (what the direct kernels take)."""
+    return s.groups == 1 and _unit_conv(s) and s.R == s.S == r and s.ph == s.pw == p
+
+
+def _tile_rows_fit(s: ConvSpec, extra: int, lds_bytes: int) -> bool:
+    """Do the input rows one 192-pixel output tile touches (``extra``: window and ragged start) fit in LDS?"""
+    return min(s.H, (191 + s.Q - 1) // s.Q + extra) * s.W * s.C * 2 <= lds_bytes
+
+
 def _weight_kpad(w: torch.Tensor, s: ConvSpec) -> tuple[torch.Tensor, int]:
     """Weights as [K, Kpad] bf16 with K-dim (r, s, c) zero-padded to a multiple of 8."""
     kred = s.R * s.S * s.Cg
@@ -92,8 +116,8 @@ def _im2col(x: torch.Tensor, s: ConvSpec, g: int, kpad: int) -> torch.Tensor:
     return col
 
 
-def _geom(s: ConvSpec) -> ConvGeom:
-    return ConvGeom(s.N, s.H, s.W, s.C, s.P, s.Q, s.R, s.S, s.sh, s.sw, s.ph, s.pw, s.dh, s.dw, s.Cg)
+def _geom(s: ConvSpec, ldx: int | None = None) -> ConvGeom:  # ldx: pixel stride of a channel-sliced input
+    return ConvGeom(s.N, s.H, s.W, s.C if ldx is None else ldx, s.P, s.Q, s.R, s.S, s.sh, s.sw, s.ph, s.pw, s.dh, s.dw, s.Cg)
 
 
 def _s2d_plan(s: ConvSpec):
@@ -123,10 +147,15 @@ def _s2d_input(x, s: ConvSpec, plan):
     return x2
 
 
+def _s2d_cached(entry, x):
+    """x2 of a ConvScratch entry (x.data_ptr(), x._version, x2) if made from this x, unwritten since, else None."""
+    return entry[2] if entry is not None and entry[:2] == (x.data_ptr(), x._version) else None
+
+
 def _slice_ok(s: ConvSpec) -> bool:
     """Convs whose input may be / output may go to a channel slice of a wider NHWC
     tensor: ungrouped implicit-GEMM products (channel offsets stay 16-B aligned)."""
-    return s.groups == 1 and _implicit_ok(s) and s.Kg % 8 == 0
+    return s.groups == 1 and _wgrad_implicit_ok(s)
 
 
 # The implicit-GEMM index decode (fp32 reciprocal division) is exact below 2^24 pixels per
@@ -146,6 +175,12 @@ def _image_chunk(s: ConvSpec) -> int:
 
 
 def conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=None):
+    """ws: optional per-layer ConvScratch kept from forward to backward (the space-to-depth
+    folded input is stored there so the weight-gradient pass does not rebuild it).
+    folded: the S2D-folded input already produced upstream (fused augment + fold); x is
+    then not read.  out: a [N, P, Q, K] channel-slice view of a wider NHWC tensor to
+    write the output into (GEMM ldc = its pixel stride: a zero-copy Concat part); x may
+    itself be such a slice."""
     nb = _image_chunk(s)
     if nb < s.N:
         y = out if out is not None else torch.empty((s.N, s.P, s.Q, s.K), dtype=BF16, device=x.device)
@@ -156,18 +191,8 @@ def conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=Non
         if ws is not None and folded is not None:
             # the chunked weight gradient must read the fused augment's folded input: the
             # NHWC data blob is not written when the fold is fused (engine.fuse_input_fold)
-            ws["s2d_full"] = (x.data_ptr(), x._version, folded)
+            ws.s2d_full = (x.data_ptr(), x._version, folded)
         return y
-    return _conv_forward(x, w, b, s, relu, ws, folded, out)
-
-
-def _conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=None):
-    """ws: optional per-layer dict kept from forward to backward (the space-to-depth
-    folded input is stored there so the weight-gradient pass does not rebuild it).
-    folded: the S2D-folded input already produced upstream (fused augment + fold); x is
-    then not read.  out: a [N, P, Q, K] channel-slice view of a wider NHWC tensor to
-    write the output into (GEMM ldc = its pixel stride: a zero-copy Concat part); x may
-    itself be such a slice."""
     ldx = chan_stride(x)
     if not (ldx and _slice_ok(s)):
         x, ldx = _c(x), s.C
@@ -183,7 +208,7 @@ def _conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=No
         call("s2d_weight", _c(w), w2, s.K, s.R, s.S, s.C, f, cp, rf, sf)
         x2 = folded if folded is not None else _s2d_input(x, s, plan)
         if ws is not None:
-            ws["s2d"] = (x.data_ptr(), x._version, x2)
+            ws.s2d = (x.data_ptr(), x._version, x2)
         return conv_forward(x2, w2, b, s2, relu, out=out)
     M = s.N * s.P * s.Q
     if out is not None:
@@ -227,9 +252,7 @@ def _conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=No
         return y
     if _implicit_ok(s):
         kred = s.R * s.S * s.Cg
-        g = _geom(s)
-        g.C = ldx  # pixel stride of the (possibly channel-sliced) input
-        A = Im2col(x, g, kcontig=True, gstride=s.Cg)
+        A = Im2col(x, _geom(s, ldx), kcontig=True, gstride=s.Cg)
         B = Dense(_c(w.reshape(s.K, kred)), kred, True, gstride=s.Kg * kred)
         gemm(M, s.Kg, kred, A, B, y, ldy, epi=EPI_BF16, groups=s.groups, c_gstride=s.Kg, bias=b, relu=relu)
         return y
@@ -248,22 +271,18 @@ def _conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=No
 # Direct 3x3 / stride-1 conv (csrc/kernels/conv3x3.hip: resident weights, input patch in LDS)
 # instead of the implicit GEMM for two thin shapes: 64 -> 64 channels with pad 1 (VGG-16's
 # conv1_2 forward and data gradient) and 48 -> 96 with pad 0 (CaffeNet / AlexNet conv1 after
-# the space-to-depth fold)
+# the space-to-depth fold); SN_FEATURES=conv_direct_c64=0 / conv_direct_k96=0 keep the GEMM
 _DIRECT_C64 = features.enabled("conv_direct_c64")
 _DIRECT_K96 = features.enabled("conv_direct_k96")
 
 
 def direct_c64_ok(s: ConvSpec) -> bool:
-    return (_DIRECT_C64 and s.C == 64 and s.K == 64 and s.groups == 1 and s.R == 3 and s.S == 3 and s.sh == 1
-            and s.sw == 1 and s.ph == 1 and s.pw == 1 and s.dh == 1 and s.dw == 1)
+    return _DIRECT_C64 and s.C == 64 and s.K == 64 and _plain_window(s, 3, 1)
 
 
 def direct_conv_ok(s: ConvSpec) -> bool:
     """Forward products the direct kernel takes (the data gradient: direct_c64_ok only)."""
-    if direct_c64_ok(s):
-        return True
-    return (_DIRECT_K96 and s.C == 48 and s.K == 96 and s.groups == 1 and s.R == 3 and s.S == 3 and s.sh == 1
-            and s.sw == 1 and s.ph == 0 and s.pw == 0 and s.dh == 1 and s.dw == 1)
+    return direct_c64_ok(s) or (_DIRECT_K96 and s.C == 48 and s.K == 96 and _plain_window(s, 3, 0))
 
 
 # 3x3 / stride-1 / pad-1 convolutions with <= 64 input channels and a multiple of 96 (> 96)
@@ -274,6 +293,10 @@ def direct_conv_ok(s: ConvSpec) -> bool:
 _DIRECT96 = features.enabled("conv_direct96")
 
 
+def direct96_split_ok(s: ConvSpec) -> bool:
+    return _DIRECT96 and 0 < s.C <= 64 and s.C % 8 == 0 and s.K > 96 and s.K % 96 == 0 and _plain_window(s, 3, 1)
+
+
 # 1x1 convolutions with <= 64 inputs and 64 outputs (GoogLeNet's conv2/3x3_reduce) on the
 # tap-packed direct kernel's <1, 64> instance (SN_FEATURES=conv_packed11=1; measured in
 # profiles/r5_packed11.txt)
@@ -281,15 +304,8 @@ _PACKED11 = features.enabled("conv_packed11")
 
 
 def packed11_conv_ok(s: ConvSpec) -> bool:
-    return (_PACKED11 and 0 < s.C <= 64 and s.C % 8 == 0 and s.K == 64 and s.groups == 1 and s.R == 1
-            and s.S == 1 and s.sh == 1 and s.sw == 1 and s.ph == 0 and s.pw == 0 and s.dh == 1 and s.dw == 1
-            and s.W * s.C * 2 * min(s.H, (191 + s.W - 1) // s.W + 1) <= 36864)
-
-
-def direct96_split_ok(s: ConvSpec) -> bool:
-    return (_DIRECT96 and 0 < s.C <= 64 and s.C % 8 == 0 and s.K > 96 and s.K % 96 == 0 and s.groups == 1
-            and s.R == 3 and s.S == 3 and s.sh == 1 and s.sw == 1 and s.ph == 1 and s.pw == 1 and s.dh == 1
-            and s.dw == 1)
+    return (_PACKED11 and 0 < s.C <= 64 and s.C % 8 == 0 and s.K == 64 and _plain_window(s, 1, 0)
+            and _tile_rows_fit(s, 1, 36864))
 
 
 # CaffeNet / AlexNet conv1 after the fold (48 -> 96, 3x3, pad 0) on the tap-packed direct kernel
@@ -299,11 +315,8 @@ _PACKED = features.enabled("conv_packed")
 
 
 def packed_conv_ok(s: ConvSpec) -> bool:
-    if not (_PACKED and s.K == 96 and 0 < s.C <= 48 and s.C % 8 == 0 and s.groups == 1 and s.R == 3 and s.S == 3
-            and s.sh == 1 and s.sw == 1 and s.ph == 0 and s.pw == 0 and s.dh == 1 and s.dw == 1 and s.Q > 0):
-        return False
-    rows = min(s.H, (191 + s.Q - 1) // s.Q + 3)  # input rows one 192-pixel tile touches
-    return rows * s.W * s.C * 2 <= 38400 and s.P * s.Q * 96 < 2 ** 31
+    return (_PACKED and s.K == 96 and 0 < s.C <= 48 and s.C % 8 == 0 and _plain_window(s, 3, 0) and s.Q > 0
+            and _tile_rows_fit(s, 3, 38400) and s.P * s.Q * 96 < 2 ** 31)
 
 
 # GoogLeNet conv1 after the 2x2 fold (115 x 115 x 16 -> 112 x 112 x 64, 4x4 taps, pad 0) on the
@@ -314,11 +327,8 @@ _PACKED44 = features.enabled("conv_packed44")
 
 
 def packed44_conv_ok(s: ConvSpec) -> bool:
-    if not (_PACKED44 and s.K == 64 and s.C in (8, 16) and s.groups == 1 and s.R == 4 and s.S == 4
-            and s.sh == 1 and s.sw == 1 and s.ph == 0 and s.pw == 0 and s.dh == 1 and s.dw == 1 and s.Q > 0):
-        return False
-    rows = min(s.H, (191 + s.Q - 1) // s.Q + 4)  # input rows one 192-pixel tile touches
-    return rows * s.W * s.C * 2 <= 22528 and s.P * s.Q * 64 < 2 ** 31
+    return (_PACKED44 and s.K == 64 and s.C in (8, 16) and _plain_window(s, 4, 0) and s.Q > 0
+            and _tile_rows_fit(s, 4, 22528) and s.P * s.Q * 64 < 2 ** 31)
 
 
 # VGG-16 conv1_1 after its fold (226 x 226 x 8 -> 224 x 224 x 64, 3x3, pad 0) on the tap-packed
@@ -328,11 +338,8 @@ _PACKED_K64 = features.enabled("conv_packed_k64")
 
 
 def packed3x3k64_ok(s: ConvSpec) -> bool:
-    if not (_PACKED_K64 and s.K == 64 and s.C == 8 and s.groups == 1 and s.R == 3 and s.S == 3
-            and s.sh == 1 and s.sw == 1 and s.ph == 0 and s.pw == 0 and s.dh == 1 and s.dw == 1 and s.Q > 0):
-        return False
-    rows = min(s.H, (191 + s.Q - 1) // s.Q + 3)  # input rows one 192-pixel tile touches
-    return rows * s.W * s.C * 2 <= 16384 and s.P * s.Q * 64 < 2 ** 31
+    return (_PACKED_K64 and s.K == 64 and s.C == 8 and _plain_window(s, 3, 0) and s.Q > 0
+            and _tile_rows_fit(s, 3, 16384) and s.P * s.Q * 64 < 2 ** 31)
 
 
 # the e4m3 direct kernel (csrc/kernels/conv3x3_fp8.hip) for the same 64 -> 64 products under
@@ -379,8 +386,45 @@ def _side_covers(t: torch.Tensor) -> bool:
 def dgrad_uses_flip(s: ConvSpec) -> bool:
     """Does conv_backward compute this conv's data gradient as a forward conv over
     flip-transposed weights (the path FlipBatch pre-computes the weights for)?"""
-    return (s.sh == 1 and s.sw == 1 and s.dh == 1 and s.dw == 1 and _implicit_ok(s) and s.Kg % 8 == 0
-            and not DGRAD_INPLACE_WEIGHTS)
+    return _dgrad_flip_geom_ok(s) and not DGRAD_INPLACE_WEIGHTS
+
+
+class Fp8Dgrad(NamedTuple):
+    """Request for an e4m3 data gradient (engine.enable_fp8): the delayed-scaling table, the slots of dy and
+    of the flipped weights, the Fp8Side of the layer above's backward if that stored dy's fp8 bytes."""
+    scales: object
+    dy_slot: int
+    wt_slot: int
+    dy_side: object = None
+
+    @property
+    def dy_only(self) -> bool:  # dy exists only as those bytes (a max pooling's side_only): no bf16 tensor
+        return bool(getattr(self.dy_side, "only", False))
+
+
+class Fp8Wgrad(NamedTuple):
+    """Request for an fp8 weight gradient: the table, x's slot, x's e4m3 copy kept from the forward, dy's slot."""
+    scales: object
+    x_slot: int
+    xq: torch.Tensor
+    dy_slot: int
+
+
+@dataclasses.dataclass
+class ConvScratch:
+    """What a convolution's forward keeps for its backward, and what its layer asks of and gets from conv_backward."""
+    # kept by conv_forward: the folded input (_s2d_cached); s2d_full: of a chunked batch folded upstream
+    s2d: tuple | None = None
+    s2d_full: tuple | None = None
+    # set by the layer before each conv_backward
+    wt: torch.Tensor | None = None       # the flip-transposed weights (FlipBatch)
+    fp8_dgrad: Fp8Dgrad | None = None
+    fp8_wgrad: Fp8Wgrad | None = None
+    fp8_dx_side: tuple | None = None     # (slot, e5m2, part): store dx as fp8 too; conv_backward takes it
+    fp8_dx_side_out: object = None       # set by conv_backward, taken by the layer: that fp8 copy's Fp8Side
+
+    def release(self) -> None:  # drop every tensor held (engine.release_activations)
+        self.__init__()
 
 
 class FlipBatch:
@@ -427,66 +471,52 @@ def _pad_cols(t2: torch.Tensor, n: int) -> torch.Tensor:
 
 def conv_backward(dy, x, w, s: ConvSpec, need_dx: bool, dw=None, db=None, gate=None, ws=None,
                   dw_acc=True, db_acc=True, dx_out=None):
-    """``dx_out``: write the data gradient there — contiguous, or a channel slice of a wider
-    NHWC buffer, which the stride-1 implicit dgrad writes in place (ldc = the slice's pixel
-    stride)."""
-    if dx_out is not None and need_dx:
-        if chan_stride(dx_out) == s.C or (_implicit_ok(s) and s.sh == s.sw == 1 and s.dh == s.dw == 1
-                                          and s.Kg % 8 == 0 and chan_stride(dx_out) and _image_chunk(s) >= s.N
-                                          and not (ws and ("fp8_dgrad" in ws or "fp8_dx_side" in ws))):
-            return _conv_backward_chunked(dy, x, w, s, need_dx, dw, db, gate, ws, dw_acc, db_acc, dx_out)
-        dx = conv_backward(dy, x, w, s, need_dx, dw, db, gate, ws, dw_acc, db_acc)
-        dx_out.copy_(dx)
-        return dx_out
-    side_req = ws.pop("fp8_dx_side", None) if ws else None
-    if side_req is not None and need_dx:
-        # the data-gradient GEMM epilogue also stores dx as fp8 for the layer below's fp8 data
-        # gradient (engine.fuse_fp8_quant); ws["fp8_dx_side_out"] is that fp8 copy's Fp8Side
-        from .gemm import Fp8Side, fp8_side_output
-        dx = torch.empty((s.N, s.H, s.W, s.C), dtype=BF16, device=x.device)
-        side = Fp8Side(dx, *side_req)
-        with fp8_side_output(side):
-            out = _conv_backward_chunked(dy, x, w, s, need_dx, dw, db, gate, ws, dw_acc, db_acc, dx)
-        ws["fp8_dx_side_out"] = side if out is dx else None
-        return out
-    return _conv_backward_chunked(dy, x, w, s, need_dx, dw, db, gate, ws, dw_acc, db_acc)
-
-
-def _conv_backward_chunked(dy, x, w, s: ConvSpec, need_dx: bool, dw=None, db=None, gate=None, ws=None,
-                           dw_acc=True, db_acc=True, dx=None):
-    nb = _image_chunk(s)
-    if nb < s.N:
-        if dx is None:
-            dx = torch.empty((s.N, s.H, s.W, s.C), dtype=BF16, device=x.device) if need_dx else None
-        full = ws.get("s2d_full") if ws else None
-        if full is not None and not (full[0] == x.data_ptr() and full[1] == x._version):
-            full = None
-        dyq_full = _fp8_dyq(dy, ws, s) if ws else None  # one fp8 copy of dy shared by the chunks
-        for n0 in range(0, s.N, nb):
-            n1 = min(s.N, n0 + nb)
-            cws = {k: ws[k] for k in ("wt", "fp8_dgrad") if k in ws} if ws else None
-            if dyq_full is not None:
-                cws["fp8_dyq"] = dyq_full[n0:n1]
-            if ws and "fp8_wgrad" in ws:
-                sc, ix, xq, idy = ws["fp8_wgrad"]
-                cws["fp8_wgrad"] = (sc, ix, xq[n0:n1], idy)
-            if full is not None:
-                xc = x[n0:n1]
-                cws["s2d"] = (xc.data_ptr(), xc._version, full[2][n0:n1])
-            _conv_backward(dy[n0:n1], x[n0:n1], w, s.with_batch(n1 - n0), need_dx, dw,
-                           db, gate[n0:n1] if gate is not None else None, cws, dw_acc, db_acc,
-                           dx_out=dx[n0:n1] if need_dx else None)
-            dw_acc = db_acc = True  # later chunks accumulate into the weight gradients
-        return dx
-    return _conv_backward(dy, x, w, s, need_dx, dw, db, gate, ws, dw_acc, db_acc, dx_out=dx)
-
-
-def _conv_backward(dy, x, w, s: ConvSpec, need_dx: bool, dw=None, db=None, gate=None, ws=None,
-                   dw_acc=True, db_acc=True, dx_out=None):
     """gate: optional bf16 NHWC tensor shaped like x; dx is zeroed where gate <= 0
     (the backward of a slope-0 in-place ReLU that produced x, fused into the dgrad).
     dw_acc / db_acc False: overwrite the gradient instead of accumulating (its buffer
-    was not cleared, see Net.clear_param_diffs(lazy=True))."""
+    was not cleared, see Net.clear_param_diffs(lazy=True)).
+    ``ws``: the layer's ConvScratch, with what the forward kept and the layer's requests.
+    ``dx_out``: write the data gradient there — contiguous, or a channel slice of a wider
+    NHWC buffer, which the stride-1 implicit dgrad writes in place (ldc = the slice's pixel
+    stride)."""
+    ws = ConvScratch() if ws is None else ws
+    nb = _image_chunk(s)
+    if dx_out is not None and need_dx and chan_stride(dx_out) != s.C and not (
+            _dgrad_flip_geom_ok(s) and chan_stride(dx_out) and nb >= s.N
+            and ws.fp8_dgrad is None and ws.fp8_dx_side is None):
+        dx_out.copy_(conv_backward(dy, x, w, s, need_dx, dw, db, gate, ws, dw_acc, db_acc))
+        return dx_out
+    dx, side = dx_out if need_dx else None, None
+    side_req, ws.fp8_dx_side = ws.fp8_dx_side, None
+    if side_req is not None and need_dx and dx_out is None:
+        # the dgrad epilogue also stores dx as fp8 for the layer below's fp8 dgrad (engine.fuse_fp8_quant)
+        dx = torch.empty((s.N, s.H, s.W, s.C), dtype=BF16, device=x.device)
+        side = Fp8Side(dx, *side_req)
+    with fp8_side_output(side) if side is not None else contextlib.nullcontext():
+        if nb >= s.N:
+            out = _conv_backward(dy, x, w, s, need_dx, dw, db, gate, ws, None, dw_acc, db_acc, dx)
+        else:
+            if dx is None and need_dx:
+                dx = torch.empty((s.N, s.H, s.W, s.C), dtype=BF16, device=x.device)
+            out = dx
+            full = _s2d_cached(ws.s2d_full, x)
+            dyq = _fp8_dyq(dy, ws)  # one fp8 copy of dy shared by the chunks
+            f8w = ws.fp8_wgrad
+            for n0 in range(0, s.N, nb):
+                n1 = min(s.N, n0 + nb)
+                cws = ConvScratch(wt=ws.wt, fp8_dgrad=ws.fp8_dgrad,
+                                  fp8_wgrad=f8w and f8w._replace(xq=f8w.xq[n0:n1]),
+                                  s2d=full if full is None else (x[n0:n1].data_ptr(), x._version, full[n0:n1]))
+                _conv_backward(dy[n0:n1], x[n0:n1], w, s.with_batch(n1 - n0), need_dx, dw, db,
+                               gate[n0:n1] if gate is not None else None, cws,
+                               None if dyq is None else dyq[n0:n1], dw_acc, db_acc, dx[n0:n1] if need_dx else None)
+                dw_acc = db_acc = True  # later chunks accumulate into the weight gradients
+    ws.fp8_dx_side_out = side if out is dx else None
+    return out
+
+
+def _conv_backward(dy, x, w, s: ConvSpec, need_dx, dw, db, gate, ws: ConvScratch, dyq, dw_acc, db_acc, dx_out):
+    """One launch's worth of images.  dyq: dy's fp8 bytes where the caller has them already."""
     kred = s.R * s.S * s.Cg
     plan = _s2d_plan(s) if s.Kg % 8 == 0 else None
     ldd, ldx = chan_stride(dy), chan_stride(x)
@@ -498,30 +528,23 @@ def _conv_backward(dy, x, w, s: ConvSpec, need_dx: bool, dw=None, db=None, gate=
     dy2 = dy.view(M, s.K) if ldd == s.K else dy
     # the bias gradient rides on the weight-gradient GEMM (ones column) on its implicit
     # paths; otherwise (no dw, explicit im2col) it is a separate column sum
-    fused_db = db is not None and dw is not None and (
-        plan is not None or (_implicit_ok(s) and s.Kg % 8 == 0))
-    f8w = ws.get("fp8_wgrad") if ws is not None else None
+    fused_db = db is not None and dw is not None and (plan is not None or _wgrad_implicit_ok(s))
+    f8w = ws.fp8_wgrad
     if (f8w is not None and dw is not None and plan is None and ldd == s.K and ldx == s.C
-            and fp8_wgrad_ok(s) and f8w[2].shape[0] == s.N):
-        dyq = ws.get("fp8_dyq")
+            and fp8_wgrad_ok(s) and f8w.xq.shape[0] == s.N):
         if dyq is None:
-            dyq = ws["fp8_dyq"] = _fp8_dyq(dy, ws, s)
+            dyq = _fp8_dyq(dy, ws)
         _conv_wgrad_fp8(dy2, dyq, s, M, kred, f8w, dw, db, dw_acc, db_acc, _dy_fp8_only(ws))
-        dw = None
-        if db is not None:
-            db, fused_db = None, False
+        dw, db, fused_db = None, None, False
     if (dw is not None or db is not None) and _dy_fp8_only(ws):
         _no_bf16_dy("a bf16 weight / bias gradient")
     _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, ldd, ldx)
-    if not need_dx:
-        return None
-    return _conv_dgrad(dy, x, w, s, M, gate, ws, ldd, ldx, dx_out)
+    return _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out) if need_dx else None
 
 
-def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, ldd=0, ldx=0):
-    ldd, ldx = ldd or s.K, ldx or s.C
+def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, ldd, ldx):
     if ((dw is not None or db is not None) and plan is None and ldd == s.K and ldx == s.C and depthwise_ok(s)
-            and _dw_io_ok(dy2, x) and not _dy_fp8_only(ws)):
+            and _dw_io_ok(dy2, x)):
         # tap sums and the bias gradient in one pass over dy and x, slab partials, fixed-order finalize
         part, n = _dw_part(s, x.device)
         call("conv_dw_wgrad", dy2, x, part, n, dw, 0 if dw is None else 1 + int(dw_acc),
@@ -532,10 +555,8 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
         colsum(dy2, db, accumulate=db_acc)
     if dw is not None and plan is not None:
         f, cp, rf, sf, s2 = plan
-        cached = ws.get("s2d") if ws is not None else None
-        if cached is not None and cached[0] == x.data_ptr() and cached[1] == x._version:
-            x2 = cached[2]
-        else:
+        x2 = _s2d_cached(ws.s2d, x)
+        if x2 is None:
             x2 = _s2d_input(x, s, plan)
         k2 = rf * sf * s2.C
         dw2 = torch.empty((s.K, k2), dtype=torch.float32, device=x.device)
@@ -544,11 +565,9 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
         call("s2d_weight_grad", dw2, dw, s.K, s.R, s.S, s.C, f, cp, rf, sf, int(dw_acc))
         dw = None
     if dw is not None:
-        if _implicit_ok(s) and s.Kg % 8 == 0:
+        if _wgrad_implicit_ok(s):
             A = Dense(dy2, ldd, kcontig=False, gstride=s.Kg)
-            g = _geom(s)
-            g.C = ldx
-            B = Im2col(x, g, kcontig=False, gstride=s.Cg)
+            B = Im2col(x, _geom(s, ldx), kcontig=False, gstride=s.Cg)
             gemm(s.Kg, kred, M, A, B, dw, kred, epi=EPI_F32_ACC if dw_acc else EPI_F32, groups=s.groups,
                  c_gstride=s.Kg * kred, bias_grad=db if fused_db else None, bias_acc=db_acc)
         else:
@@ -562,10 +581,8 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
                 tmp = torch.zeros((kgp, kpad), dtype=torch.float32, device=x.device)
                 gemm(kgp, kpad, M, Dense(dyg, dyg.stride(0), False), Dense(col, kpad, False), tmp, kpad,
                      epi=EPI_F32)
-                if dw_acc:
-                    dw2[g * s.Kg:(g + 1) * s.Kg].add_(tmp[:s.Kg, :kred])
-                else:
-                    dw2[g * s.Kg:(g + 1) * s.Kg].copy_(tmp[:s.Kg, :kred])
+                dwg = dw2[g * s.Kg:(g + 1) * s.Kg]
+                (dwg.add_ if dw_acc else dwg.copy_)(tmp[:s.Kg, :kred])
 
 
 # Bias gradient of the fp8 weight-gradient products.  1 (default): a virtual e4m3 ones column
@@ -591,8 +608,6 @@ def conv_dy_fp8_only_ok(layer, s: ConvSpec) -> bool:
     (engine.fuse_fp8_quant fp8_dx_only); conv_backward raises if a bf16 read happens anyway."""
     if layer.fp8_dgrad_slots is None or not fp8_dgrad_ok(s) or _s2d_plan(s) is not None:
         return False
-    if not (s.sh == 1 and s.sw == 1 and s.dh == 1 and s.dw == 1 and _implicit_ok(s) and s.Kg % 8 == 0):
-        return False
     need_w = layer.param_grads_needed(0)
     need_b = layer.bias is not None and layer.param_grads_needed(1)
     if need_w and not (layer.fp8_wgrad and fp8_wgrad_ok(s)):
@@ -600,11 +615,8 @@ def conv_dy_fp8_only_ok(layer, s: ConvSpec) -> bool:
     return not need_b or (need_w and (s.R * s.S * s.Cg) % 16 == 0 and FP8_WGRAD_BIAS)
 
 
-def _dy_fp8_only(ws) -> bool:
-    """The output gradient exists only as the fp8 side output of the layer above (a max
-    pooling's backward with side_only): its bf16 tensor was never written."""
-    f8 = ws.get("fp8_dgrad") if ws else None
-    return bool(f8 is not None and len(f8) > 3 and f8[3] is not None and getattr(f8[3], "only", False))
+def _dy_fp8_only(ws: ConvScratch) -> bool:
+    return ws.fp8_dgrad is not None and ws.fp8_dgrad.dy_only
 
 
 def _no_bf16_dy(what: str):
@@ -612,20 +624,14 @@ def _no_bf16_dy(what: str):
                        "above stored only as fp8 (engine.fuse_fp8_quant fp8_dx_only; SN_FEATURES=fp8_dx_only=0)")
 
 
-def _fp8_dyq(dy, ws, s):
+def _fp8_dyq(dy, ws: ConvScratch):
     """fp8 bytes of the output gradient for this layer's fp8 data / weight gradients: the
     side output of the layer above's dgrad epilogue when it covers dy, else one pass."""
-    f8 = ws.get("fp8_dgrad") if ws else None
-    f8w = ws.get("fp8_wgrad") if ws else None
+    f8, f8w = ws.fp8_dgrad, ws.fp8_wgrad
     if f8 is None and f8w is None:
         return None
-    if f8 is not None:
-        sc, idy = f8[0], f8[1]
-        side = f8[3] if len(f8) > 3 else None
-    else:
-        sc, idy, side = f8w[0], f8w[3], None
+    sc, idy, side = (f8.scales, f8.dy_slot, f8.dy_side) if f8 is not None else (f8w.scales, f8w.dy_slot, None)
     e5 = sc.is_e5m2(idy)
-    from .gemm import side_bytes
     dyq = side_bytes(side, dy, e5)
     if dyq is None and _dy_fp8_only(ws):
         _no_bf16_dy("quantising dy")
@@ -655,51 +661,45 @@ def _conv_wgrad_fp8(dy2, dyq, s, M, kred, f8w, dw, db, dw_acc, db_acc, dy_fp8_on
          bias_grad=db if fused_db else None, bias_acc=db_acc)
 
 
-def _conv_dgrad(dy, x, w, s, M, gate, ws, ldd=0, ldx=0, dx_out=None):
-    ldd, ldx = ldd or s.K, ldx or s.C
+def _flipped(w, s, pre):  # the flip-transposed weights: pre (flipped once for the net, FlipBatch) or one pass
+    if pre is not None:
+        return pre
+    wt = torch.empty((s.groups, s.Cg, s.R, s.S, s.Kg), dtype=BF16, device=w.device)
+    call("flip_weights", _c(w), wt, s.groups, s.Kg, s.R, s.S, s.Cg)
+    return wt
+
+
+def _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out):
     dx = dx_out if dx_out is not None else torch.empty((s.N, s.H, s.W, s.C), dtype=BF16, device=x.device)
     ldo = chan_stride(dx)  # C, or the pitch of a channel-slice destination (conv_backward dx_out)
     if gate is not None and chan_stride(gate) != ldo:  # the gate (= x) must share dx's layout
         gate = _c(gate)
-    if _dy_fp8_only(ws) and not (s.sh == 1 and s.sw == 1 and s.dh == 1 and s.dw == 1 and _implicit_ok(s)
-                                 and s.Kg % 8 == 0):
+    flip = _dgrad_flip_geom_ok(s)
+    fp8 = flip and ws.fp8_dgrad is not None and fp8_dgrad_ok(s) and ldd == s.K
+    if _dy_fp8_only(ws) and not fp8:
         _no_bf16_dy("a bf16 data gradient")
-    if s.sh == 1 and s.sw == 1 and s.dh == 1 and s.dw == 1 and _implicit_ok(s) and s.Kg % 8 == 0:
+    if flip:
         # dgrad == forward conv of dy with flipped / transposed weights, pad' = R-1-pad.
         # A flip pass + KC (ds_read_b128) B operand measures faster than reading the
         # weights in place through the FLIPW operand (MC, tr_b16 reads): 81k vs 86k img/s
         # on CaffeNet; FLIPW stays available via DGRAD_INPLACE_WEIGHTS.
         g2 = ConvGeom(s.N, s.P, s.Q, ldd, s.H, s.W, s.R, s.S, 1, 1, s.R - 1 - s.ph, s.S - 1 - s.pw, 1, 1, s.Kg)
         kr2 = s.R * s.S * s.Kg
-        pre = ws.get("wt") if ws is not None else None  # flipped once for the net (FlipBatch)
-        f8 = ws.get("fp8_dgrad") if ws is not None else None
-        if f8 is not None and fp8_dgrad_ok(s) and ldd == s.K:
-            return _conv_dgrad_fp8(dy, w, s, g2, kr2, pre, gate, dx, f8, ws.get("fp8_dyq"))
-        if _dy_fp8_only(ws):
-            _no_bf16_dy("a bf16 data gradient")
+        if fp8:
+            return _conv_dgrad_fp8(dy, w, s, g2, kr2, gate, dx, ws, dyq)
         if (direct_c64_ok(s) and ldd == s.K and ldx == s.C and dy.is_contiguous() and dx.is_contiguous()
                 and not DGRAD_INPLACE_WEIGHTS and not _side_covers(dx)):
-            if pre is None:
-                pre = torch.empty((s.groups, s.Cg, s.R, s.S, s.Kg), dtype=BF16, device=x.device)
-                call("flip_weights", _c(w), pre, s.groups, s.Kg, s.R, s.S, s.Cg)
-            call("conv3x3_direct", dy, pre, None, _c(gate) if gate is not None else None, dx, s.N, s.H, s.W, 64, 64, 1,
-                 0, 0)
+            call("conv3x3_direct", dy, _flipped(w, s, ws.wt), None, _c(gate) if gate is not None else None, dx,
+                 s.N, s.H, s.W, 64, 64, 1, 0, 0)
             return dx
         A = Im2col(dy, g2, kcontig=True, gstride=s.Kg)
         if DGRAD_INPLACE_WEIGHTS:
             B = FlipW(_c(w), s.Kg, s.R, s.S, s.Cg)
         else:
-            if pre is not None:
-                wt = pre
-            else:
-                wt = torch.empty((s.groups, s.Cg, s.R, s.S, s.Kg), dtype=BF16, device=x.device)
-                call("flip_weights", _c(w), wt, s.groups, s.Kg, s.R, s.S, s.Cg)
-            B = Dense(wt.view(s.C, kr2), kr2, True, gstride=s.Cg * kr2)
-        gemm(s.N * s.H * s.W, s.Cg, kr2, A, B, dx, ldo, epi=EPI_BF16, groups=s.groups, c_gstride=s.Cg,
-             gate=gate)
+            B = Dense(_flipped(w, s, ws.wt).view(s.C, kr2), kr2, True, gstride=s.Cg * kr2)
+        gemm(s.N * s.H * s.W, s.Cg, kr2, A, B, dx, ldo, epi=EPI_BF16, groups=s.groups, c_gstride=s.Cg, gate=gate)
         return dx
-    if (ldd == s.K and depthwise_ok(s) and _dw_io_ok(dy, w, dx, gate) and not _side_covers(dx)
-            and not _dy_fp8_only(ws)):
+    if ldd == s.K and depthwise_ok(s) and _dw_io_ok(dy, w, dx, gate) and not _side_covers(dx):
         call("conv_dw_dgrad", dy, w, gate, dx, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
         return dx
     # generic: dcol = dy_g @ W_g, then col2im (gather, no atomics)
@@ -733,28 +733,18 @@ def fp8_dgrad_ok(s: ConvSpec) -> bool:
     return dgrad_uses_flip(s) and s.Kg % 16 == 0 and s.C % 8 == 0
 
 
-def _conv_dgrad_fp8(dy, w, s, g2, kr2, wt, gate, dx, f8, ws_dyq=None):
+def _conv_dgrad_fp8(dy, w, s, g2, kr2, gate, dx, ws: ConvScratch, dyq):
     """Data gradient as an e4m3 forward conv of the output gradient with the flip-
     transposed weights (v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulation): the output
     gradient (e4m3, or e5m2 when its slot says so) and the flipped weights are quantised
-    per tensor with their own delayed-
-    scaling slots (a slot not yet initialised scales from the current tensor), the
-    epilogue dequantises and applies the ReLU-backward gate, dx stays bf16.  The weight
-    gradient keeps reading the bf16 output gradient."""
-    sc, idy, iwt = f8[:3]
-    if wt is None:
-        wt = torch.empty((s.groups, s.Cg, s.R, s.S, s.Kg), dtype=BF16, device=dy.device)
-        call("flip_weights", _c(w), wt, s.groups, s.Kg, s.R, s.S, s.Cg)
+    per tensor with their own delayed-scaling slots (a slot not yet initialised scales from
+    the current tensor), the epilogue dequantises and applies the ReLU-backward gate, dx stays
+    bf16.  dyq: dy's fp8 bytes if the weight gradient or the chunk loop made them already."""
+    sc, idy, iwt, _ = ws.fp8_dgrad
+    wt = _flipped(w, s, ws.wt)
     e5 = sc.is_e5m2(idy)
-    dyq = ws_dyq
     if dyq is None:
-        side = f8[3] if len(f8) > 3 else None  # dy's fp8 bytes stored by the layer above's dgrad epilogue
-        from .gemm import side_bytes
-        dyq = side_bytes(side, dy, e5)
-    if dyq is None:
-        if len(f8) > 3 and getattr(f8[3], "only", False):
-            _no_bf16_dy("quantising dy for the data gradient")
-        dyq = quant_fp8(dy, sc.slot(idy), e5m2=e5)
+        dyq = _fp8_dyq(dy, ws)
     wtq = quant_fp8(wt, sc.slot(iwt))
     if direct_fp8_ok(s) and not e5 and dx.is_contiguous() and not _side_covers(dx):
         call("conv3x3_fp8", _c(dyq), wtq, sc.deq(idy), sc.deq(iwt), None, _c(gate) if gate is not None else None, dx,

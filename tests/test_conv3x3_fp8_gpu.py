@@ -2,7 +2,7 @@
 channels, stride 1, pad 1) against fp32 PyTorch convolutions of the same dequantised
 values: forward (bias, ReLU), data gradient (flip-transposed weights, ReLU-backward gate),
 ragged spatial edges (partial 16 x 16 tiles), and more tiles than CUs (the persistent loop
-with its cross-tile patch prefetch).  The GEMM path (SN_CONV_DIRECT_FP8=0 equivalent) on the
+with its cross-tile patch prefetch).  The GEMM path (SN_FEATURES=conv_direct_fp8=0 equivalent) on the
 same bytes must agree too."""
 import pytest
 import torch
@@ -75,7 +75,7 @@ def test_direct_fp8_dgrad(gpu, N, H, W, gated, monkeypatch):
     dy = (torch.randn(N, H, W, 64, device=gpu, generator=gen) * 1e-4).to(torch.bfloat16)
     gate = x if gated else None
     sc = hip.Fp8Scales(2, gpu)
-    dx8 = hip.conv_backward(dy, x, w, s, True, ws={"fp8_dgrad": (sc, 0, 1)}, gate=gate)
+    dx8 = hip.conv_backward(dy, x, w, s, True, ws=hip.ConvScratch(fp8_dgrad=hip.Fp8Dgrad(sc, 0, 1)), gate=gate)
     ref = F.conv_transpose2d(dy.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2),
                              padding=1).permute(0, 2, 3, 1)
     if gated:

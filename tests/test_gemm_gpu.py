@@ -214,7 +214,7 @@ def test_fp8_conv_dgrad(gpu, case, fmt, tile, monkeypatch):
     if fmt == "e5m2":
         sc.set_e5m2(0)
     assert hip.fp8_dgrad_ok(s)
-    dx8 = hip.conv_backward(dy, x, w, s, True, ws={"fp8_dgrad": (sc, 0, 1)}, gate=gate)
+    dx8 = hip.conv_backward(dy, x, w, s, True, ws=hip.ConvScratch(fp8_dgrad=hip.Fp8Dgrad(sc, 0, 1)), gate=gate)
     dxb = hip.conv_backward(dy, x, w, s, True, gate=gate)
     ref = F.conv_transpose2d(dy.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), padding=1,
                              groups=g).permute(0, 2, 3, 1)

@@ -275,7 +275,7 @@ def test_fused_fold_weight_gradient_with_image_chunks(gpu, monkeypatch):
     grads = []
     for max_pix in (1 << 24, 2 * 34 * 34):  # whole batch / 2-image chunks
         monkeypatch.setattr(hip, "_MAX_PIX", max_pix)
-        ws = {}
+        ws = hip.ConvScratch()
         hip.conv_forward(stale, w, None, s, ws=ws, folded=folded)
         dw = torch.zeros(64, 3, 3, 3, device=gpu)
         hip.conv_backward(dy, stale, w, s, False, dw, None, ws=ws, dw_acc=True)
@@ -404,7 +404,7 @@ def test_googlenet_zero_copy_concat_bitwise(gpu, monkeypatch):
 def test_fp8_layer_selection_threshold(gpu, direct, monkeypatch):
     """enable_fp8's default cost-model threshold keeps a 10-way fc8 in bf16 and everything
     else eligible in e4m3; VGG's conv1_2 (576 MACs per input element, below the threshold)
-    is chosen only for the e4m3 direct kernel (SN_CONV_DIRECT_FP8, default on)."""
+    is chosen only for the e4m3 direct kernel (SN_FEATURES=conv_direct_fp8, default on)."""
     from sparknet_amd.core.solver import Solver
     from sparknet_amd.engine import enable_fp8
     from sparknet_amd.ops import hip
