@@ -108,7 +108,8 @@ def main():
         ua, ub = sorted(res[args.a])[len(res[args.a]) // 2], sorted(res[args.b])[len(res[args.b]) // 2]
         tot[args.a] += ua
         tot[args.b] += ub
-        print(f"{name:24s} {a[0]:8d} {a[1]:5d} {a[2]:6d} {a[3]} {a[16]:4d} {a[17]:3d}  {ua:8.1f} {ub:8.1f}  {ub / ua:.3f}",
+        c, tile, splits = a[:3]  # _launch(call, tile, splits, kchunk)
+        print(f"{name:24s} {c.M:8d} {c.N:5d} {c.K:6d} {c.groups} {tile:4d} {splits:3d}  {ua:8.1f} {ub:8.1f}  {ub / ua:.3f}",
               flush=True)
     print(f"total: A({args.switch}={args.a}) {tot[args.a]:.1f} us   B({args.switch}={args.b}) {tot[args.b]:.1f} us"
           f"   B/A {tot[args.b] / tot[args.a]:.3f}")

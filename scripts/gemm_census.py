@@ -75,10 +75,8 @@ def main():
 
     rows = []
     for name, a, k in rec:
-        M, N, K, groups = a[0], a[1], a[2], a[3]
-        ops = a[4]
-        epi = a[5]
-        tile, splits, kchunk = a[16], a[17], a[18]
+        c, tile, splits, kchunk = a  # _launch(call, tile, splits, kchunk)
+        M, N, K, groups, epi = c.M, c.N, c.K, c.groups, c.epi
         fn = (lambda a=a, k=k: orig(*a, **k))
         for _ in range(3):
             fn()
@@ -95,7 +93,7 @@ def main():
         us = ts[len(ts) // 2] * 1e3
         fl = 2.0 * M * N * K * groups
         kind = {(0, 1, 0, 0): "fwd", (1, 0, 1, 1): "wgrad", (0, 1, 1, 2): "dgrad"}.get(
-            (ops[1], ops[2], ops[4], ops[5]), f"{ops[1]}{ops[2]}/{ops[4]}{ops[5]}")
+            (c.a.mc, c.a.mode, c.b.mc, c.b.mode), f"{c.a.mc}{c.a.mode}/{c.b.mc}{c.b.mode}")
         rows.append((name, kind, M, N, K, groups, tile, splits, epi, us, fl / us / 1e6))
     tot = 0.0
     print(f"{'layer:pass':24s} {'kind':7s} {'M':>8s} {'N':>5s} {'K':>6s} {'g':>2s} tile spl epi {'us':>8s} {'TF/s':>7s}")

@@ -91,9 +91,9 @@ def main():
     rec = []
     orig = G._launch
 
-    def spy(*a, **k):
-        rec.append((where[0], a, k))
-        return orig(*a, **k)
+    def spy(call, tile, splits, kchunk):
+        rec.append((where[0], call, tile, splits, kchunk))
+        return orig(call, tile, splits, kchunk)
     G._launch = spy
     trainer.local_step()
     torch.cuda.synchronize()
@@ -102,18 +102,10 @@ def main():
     updates = {}
     tot_old = tot_new = 0.0
     seen = set()
-    for name, a, k in rec:
-        a = list(a)
-        M, N, K, groups, ops, epi, out = a[0], a[1], a[2], a[3], a[4], a[5], a[6]
-        gate, bias_grad, tile, splits, kchunk = a[11], a[12], a[16], a[17], a[18]
-        deq = a[19] if len(a) > 19 else k.get("deq")
-        xtra = a[20] if len(a) > 20 else k.get("xtra", G._NO_XTRA)
-        if deq is not None or epi == G.EPI_SGD:
-            continue
-        sa, a_mc, a_mode, sb, b_mc, b_mode = ops
-        key = (M, N, K, groups, a_mc, a_mode, b_mc, b_mode, epi, gate is not None, bias_grad is not None,
-               bool(xtra[0]), G._geom_key(sa), G._geom_key(sb)) + (out.dtype,)
-        if key in seen:
+    for name, call, tile, splits, kchunk in rec:
+        M, N, K, groups, out, bias_grad = call.M, call.N, call.K, call.groups, call.out, call.bias_grad
+        key = call.key
+        if call.fp8 or call.epi == G.EPI_SGD or key in seen:
             continue
         seen.add(key)
         fl = 2.0 * M * N * K * groups
@@ -127,22 +119,19 @@ def main():
                 bias_grad.copy_(bsaved)
 
         def run(t, s, kc):
-            b = list(a)
-            b[16], b[17], b[18] = t, s, kc
-            orig(*b, **k)
+            orig(call, t, s, kc)
         restore()
         run(tile, splits, kchunk)
         ref = out.float().clone()
         scale = ref.abs().max().item() + 1e-6
         t_old = timed(lambda: run(tile, splits, kchunk), reps)
         best = (t_old, tile, splits, kchunk)
-        b_kc_dense = b_mc == 0 and b_mode == G.OP_DENSE
-        cands = G._candidates(M, N, K, groups, b_kc_dense, epi)
+        cands = G._candidates(call)
         if args.wide:
             extra = []
             for t in dict.fromkeys(c[0] for c in cands):
                 for s in (1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256):
-                    kc = -(-(-(-K // s)) // G.BK) * G.BK
+                    kc = G._kchunk(K, s, G.BK)
                     s2 = max(1, -(-K // kc))
                     if s2 > 1 and s2 * M * N * groups * 4 > (256 << 20):
                         continue

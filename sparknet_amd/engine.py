@@ -457,7 +457,6 @@ class _SlabGrad:
         self.solver, self.layer = solver, layer
         self.buf = None
         self.desc = None
-        self.key = None
         self.got = False
         self.table = None
 
@@ -486,11 +485,9 @@ class _SlabGrad:
         self._set(d)
 
     def _set(self, d):
-        key = None if d is None else (d["ws"].data_ptr(), d["splits"], d["M"], d["N"], d["ldw"], d["groups"],
-                                      d["ones"], d["ldc"], d["c_gstride"])
-        if key != self.key:
+        if d != self.desc:  # (a gemm.SplitSlabs compares its address and layout)
             assert not torch.cuda.is_current_stream_capturing(), "split-K slab layout changed during capture"
-            self.key, self.desc = key, d
+            self.desc = d
             self.solver.slab_tables_dirty = True
             self.table = None
             if d is not None:
@@ -516,15 +513,15 @@ class _SlabGrad:
         d = self.desc
         if d is None:
             return {}
-        M, N, ldw, G, S = d["M"], d["N"], d["ldw"], d["groups"], d["splits"]
-        assert d["ldc"] == N and d["c_gstride"] == M * N, "weight gradient must be the dense [K][RS*Cg] layout"
-        base, ss, gs = d["ws"].data_ptr(), M * ldw, S * M * ldw
+        M, N, ldw, G, S = d.M, d.N, d.ldw, d.groups, d.splits
+        assert d.ldc == N and d.c_gstride == M * N, "weight gradient must be the dense [K][RS*Cg] layout"
+        base, ss, gs = d.base, M * ldw, S * M * ldw
         wp = self.layer.weight
         out = {wp.offset: [(wp.offset + (g * M + m) * N, N, base + 4 * (g * gs + m * ldw), ss, S, 1)
                            for g in range(G) for m in range(M)]}
         bp = self.layer.bias
-        if d["ones"] >= 0 and bp is not None:
-            out[bp.offset] = [(bp.offset + g * M, M, base + 4 * (g * gs + d["ones"]), ss, S, ldw) for g in range(G)]
+        if d.ones >= 0 and bp is not None:
+            out[bp.offset] = [(bp.offset + g * M, M, base + 4 * (g * gs + d.ones), ss, S, ldw) for g in range(G)]
         return out
 
 

@@ -18,7 +18,7 @@ import contextlib
 import ctypes as C
 import json
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field, replace
 
 import torch
 
@@ -84,19 +84,28 @@ class FlipW:
 FP8 = torch.uint8  # e4m3 bytes (torch.float8_e4m3fn tensors are viewed as uint8)
 
 
-def _operand(op, fp8: bool = False) -> tuple[_lib.SnOperand, int, int]:
+@dataclass
+class Operand:
+    """A prepared operand: the kernel's descriptor, whether its rows are the reduction axis (MC)
+    and how it is addressed (OP_*)."""
+    s: _lib.SnOperand
+    mc: int
+    mode: int
+
+
+def _operand(op, fp8: bool = False) -> Operand:
     elt = FP8 if fp8 else torch.bfloat16
     if isinstance(op, FlipW):
         assert op.w.dtype == torch.bfloat16 and op.w.is_contiguous() and op.Cg % 8 == 0
         g = _lib.SnConvGeom(0, 0, 0, op.Kg, 1, 1, op.R, op.S, 1, 1, 0, 0, 1, 1, op.Cg)
         s = _lib.SnOperand(op.w.data_ptr(), 0, op.Kg * op.R * op.S * op.Cg, g)
-        return s, 1, OP_FLIPW
+        return Operand(s, 1, OP_FLIPW)
     if isinstance(op, Dense):
         assert op.t.dtype == elt, (op.t.dtype, elt)
         assert op.t.data_ptr() % 16 == 0 and (op.ld * op.t.element_size()) % 16 == 0, \
             "dense operand must be 16-B aligned"
         s = _lib.SnOperand(op.t.data_ptr(), op.ld, op.gstride, _lib.SnConvGeom())
-        return s, 0 if op.kcontig else 1, OP_DENSE
+        return Operand(s, 0 if op.kcontig else 1, OP_DENSE)
     g = op.geom
     # contiguous NHWC, or a channel slice of a wider NHWC tensor whose pixel stride is g.C
     assert op.x.dtype == elt and (op.x.is_contiguous() or (
@@ -109,7 +118,7 @@ def _operand(op, fp8: bool = False) -> tuple[_lib.SnOperand, int, int]:
     assert g.N * g.H * g.W * g.C < (1 << 31), "implicit conv uses 32-bit element offsets"
     assert op.x.data_ptr() % 16 == 0, "implicit conv operand must be 16-B aligned"
     s = _lib.SnOperand(op.x.data_ptr(), 0, op.gstride, g.c_struct())
-    return s, 0 if op.kcontig else 1, OP_IM2COL
+    return Operand(s, 0 if op.kcontig else 1, OP_IM2COL)
 
 
 TILES = {0: (128, 128), 1: (256, 64), 2: (256, 128), 3: (128, 256), 4: (128, 96), 5: (256, 48),
@@ -173,6 +182,71 @@ def choose_splits(M: int, N: int, K: int, groups: int = 1, tile: int = 0) -> tup
     return splits, kchunk
 
 
+@dataclass
+class GemmCall:
+    """One product as gemm() was asked for it, its operands prepared: what the choice of a tile and
+    every launch read.  ``N`` counts the ones column of a fused bias gradient (``ones``: its index)."""
+    M: int
+    N: int
+    K: int
+    groups: int
+    a: Operand
+    b: Operand
+    epi: int
+    out: torch.Tensor
+    ldc: int
+    c_gstride: int = 0
+    bias: torch.Tensor | None = None
+    relu: bool = False
+    gate: torch.Tensor | None = None
+    gate_scale: float = 1.0
+    bias_grad: torch.Tensor | None = None
+    bias_acc: bool = True
+    ones: int = -1
+    sgd: dict | None = None       # EPI_SGD: gemm()'s ``sgd``
+    dropout: tuple | None = None  # (rng_state, layer stream id, ratio)
+    deq_a: torch.Tensor | None = None
+    deq_b: torch.Tensor | None = None
+    fp8_format: int = 0           # SnGemmArgs.fp8: 0 = bf16 operands
+
+    @property
+    def fp8(self) -> bool:
+        return self.fp8_format != 0
+
+    @property
+    def bk(self) -> int:  # elements of one K-step
+        return 128 if self.fp8_format else BK
+
+    @property
+    def b_kc_dense(self) -> bool:
+        return self.b.mc == 0 and self.b.mode == OP_DENSE
+
+    @property
+    def key(self) -> tuple:
+        """What the tuning database files this product under."""
+        a, b, f8 = self.a, self.b, self.fp8_format
+        return (self.M, self.N, self.K, self.groups, a.mc, a.mode, b.mc, b.mode, self.epi, self.gate is not None,
+                self.bias_grad is not None, self.dropout is not None, _geom_key(a.s), _geom_key(b.s),
+                *(("fp8",) if f8 == 1 else ("fp8", f8) if f8 else ()), self.out.dtype)
+
+
+@dataclass
+class SplitSlabs:
+    """The fp32 partial products a deferred split-K launch left for the solver (defer_reduce):
+    ``ws`` is [groups][splits][M][ldw] at address ``base``, ``N`` without the ones column,
+    ``ldc`` / ``c_gstride`` the layout of the gradient the slabs sum to."""
+    ws: torch.Tensor = field(compare=False)  # equal descriptors: the same address and layout
+    base: int
+    splits: int
+    M: int
+    N: int
+    ldw: int
+    groups: int
+    ones: int
+    ldc: int
+    c_gstride: int
+
+
 def gemm(M: int, N: int, K: int, A, B, out: torch.Tensor, ldc: int, *, epi: int,
          groups: int = 1, c_gstride: int = 0, bias: torch.Tensor | None = None, relu: bool = False,
          splits: int | None = None, gate: torch.Tensor | None = None,
@@ -198,91 +272,101 @@ def gemm(M: int, N: int, K: int, A, B, out: torch.Tensor, ldc: int, *, epi: int,
     fused Dropout backward: the gate is the dropout output)."""
     if M == 0 or N == 0:
         return
-    sg = (0, 0, 0, 0, 0.0, 0.0, 0)
     if epi == EPI_SGD:
         assert sgd is not None and groups == 1 and deq is None
         splits = 1
-        sg = (sgd["w"].data_ptr(), sgd["h"].data_ptr(), sgd["shadow"].data_ptr(), sgd["hyper"].data_ptr(),
-              float(sgd["lr_mult"]), float(sgd["decay_mult"]), int(sgd["flags"]))
     # fp8 operands; deq = (1/scale_A, 1/scale_B[, format]) device scalars, format 1 = e4m3 x e4m3
     # (default), 2 = e5m2 A x e4m3 B (SnGemmArgs.fp8)
-    fp8 = deq is not None
-    sa, a_mc, a_mode = _operand(A, fp8)
-    sb, b_mc, b_mode = _operand(B, fp8)
+    deq_a, deq_b, fp8 = (*deq, 1)[:3] if deq is not None else (None, None, 0)
+    a, b = _operand(A, bool(fp8)), _operand(B, bool(fp8))
     ones = -1
     if bias_grad is not None:
-        assert epi in (EPI_F32, EPI_F32_ACC, EPI_SGD) and b_mc == 1 and b_mode != OP_FLIPW and N % 8 == 0
-        assert not fp8 or (a_mc == 1 and N % 16 == 0)  # fp8: the MC weight-gradient products
+        assert epi in (EPI_F32, EPI_F32_ACC, EPI_SGD) and b.mc == 1 and b.mode != OP_FLIPW and N % 8 == 0
+        assert not fp8 or (a.mc == 1 and N % 16 == 0)  # fp8: the MC weight-gradient products
         assert bias_grad.dtype == torch.float32 and bias_grad.is_contiguous() and bias_grad.numel() == groups * M
         ones, N = N, N + 1
-    bk = 128 if fp8 else BK
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.is_contiguous()
-    if gate is not None:
-        assert epi == EPI_BF16 and gate.dtype == torch.bfloat16
-    xtra = (0, 0, 0.0, float(gate_scale))
-    if dropout is not None:
-        assert epi == EPI_BF16
-        rng, dstream, ratio = dropout
-        xtra = (rng.data_ptr(), int(dstream), float(ratio), float(gate_scale))
-    ops = (sa, a_mc, a_mode, sb, b_mc, b_mode)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous())
+    assert gate is None or (epi == EPI_BF16 and gate.dtype == torch.bfloat16)
+    assert dropout is None or epi == EPI_BF16
+    call =GemmCall(M, N, K, groups, a, b, epi, out, ldc, c_gstride, bias, relu, gate, float(gate_scale),
+                    bias_grad, bias_acc, ones, sgd if epi == EPI_SGD else None, dropout, deq_a, deq_b, fp8)
     if splits is not None or _FORCE_TILE >= 0:
-        if fp8:
-            tile = _FORCE_TILE if (_FORCE_TILE in _FP8_TILES and not (a_mc or b_mc)) else 0
-        else:
-            tile = _FORCE_TILE if _FORCE_TILE >= 0 else choose_tile(M, N, b_mc == 0 and b_mode == OP_DENSE)
-        if epi == EPI_SGD and tile not in (0, 1, 2, 3):
-            tile = 0
+        tile, model_splits, kchunk = _model_config(call, _FORCE_TILE)
         if splits is None:
-            splits, kchunk = choose_splits(M, N, K * BK // bk, groups, tile)
-            kchunk = kchunk * bk // BK
+            splits = model_splits
         else:
-            kchunk = -(-(-(-K // splits)) // bk) * bk
+            kchunk = _kchunk(K, splits, call.bk)
     else:
-        tile, splits, kchunk = _tuned_config(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu, gate,
-                                             bias_grad, bias_acc, ones, sg, xtra, deq)
-    _launch(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu, gate, bias_grad, bias_acc, ones, sg,
-            tile, splits, kchunk, deq, xtra)
+        tile, splits, kchunk = _tuned_config(call)
+    _launch(call, tile, splits, kchunk)
 
 
-_NO_XTRA = (0, 0, 0.0, 1.0)
+def _kchunk(K: int, splits: int, bk: int) -> int:
+    """K elements per split, in whole K-steps."""
+    return -(-(-(-K // splits)) // bk) * bk
+
+
+def _model_config(c: GemmCall, force: int = -1) -> tuple[int, int, int]:
+    """The cost model's (tile, splits, kchunk) for ``c``; ``force`` >= 0 names the tile instead
+    (where the product has an instance of it)."""
+    if c.fp8:
+        tile = force if (force in _FP8_TILES and not (c.a.mc or c.b.mc)) else 0
+    else:
+        tile = force if force >= 0 else choose_tile(c.M, c.N, c.b_kc_dense)
+    if c.epi == EPI_SGD and tile not in (0, 1, 2, 3):
+        tile = 0
+    # K counts operand elements, bk per K-step; the cost model counts bf16 K-steps
+    _, kchunk = choose_splits(c.M, c.N, c.K * BK // c.bk, c.groups, tile)
+    kchunk = kchunk * c.bk // BK
+    return tile, -(-c.K // kchunk), kchunk
+
+
 # bf16 epilogues of the 4-wave tiles store through LDS as whole 16-B row chunks
 # (SnGemmArgs.lds_store)
 _LDS_EPI = True
 _LDS_EPI_TILES = frozenset((0, 1, 4, 5, 10, 12, 13, 14, 15, 16, 17, 18, 19, 20))
-def _drop_fields(xtra):
-    """(drop_rng, drop_stream, drop_thr, drop_scale, gate_scale) of SnGemmArgs."""
-    rng, dstream, ratio, gscale = xtra
-    if not rng:
-        return (0, 0, 0, 1.0, gscale)
-    return (rng, dstream, int(4294967295 * ratio) & 0xffffffff, 1.0 / (1.0 - ratio), gscale)
 
 
-def _launch(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu, gate, bias_grad, bias_acc, ones, sg,
-            tile, splits, kchunk, deq=None, xtra=_NO_XTRA):
-    """One GEMM launch (+ the split-K reduce) with an explicit tile / split choice."""
-    sa, a_mc, a_mode, sb, b_mc, b_mode = ops
-    fp8 = deq is not None
-    bk = 128 if fp8 else BK
-    splits = max(1, -(-K // kchunk))
-    dq = (deq[0].data_ptr(), deq[1].data_ptr()) if fp8 else (0, 0)
-    f8 = (deq[2] if len(deq) > 2 else 1) if fp8 else 0
+def _ptr(t) -> int:
+    return t.data_ptr() if t is not None else 0
+
+
+def _gemm_args(c: GemmCall, tile: int, **fields) -> _lib.SnGemmArgs:
+    """The SnGemmArgs of one launch of ``c``: what the unsplit and the split launch share, then
+    ``fields``."""
     bm, bn = TILES[tile]
-    tm_, tn_ = -(-M // bm), -(-N // bn)
-    raster = int(1 < tn_ <= 8 and tm_ >= 8 * tn_)
-    gp = gate.data_ptr() if gate is not None else 0
-    bg = bias_grad.data_ptr() if bias_grad is not None else 0
+    tm, tn = -(-c.M // bm), -(-c.N // bn)
+    args = _lib.SnGemmArgs(M=c.M, N=c.N, K=c.K, groups=c.groups, a_mc=c.a.mc, a_mode=c.a.mode, b_mc=c.b.mc,
+                           b_mode=c.b.mode, A=c.a.s, B=c.b.s, tile=tile, fp8=c.fp8_format, deq_a=_ptr(c.deq_a),
+                           deq_b=_ptr(c.deq_b), raster_n=int(1 < tn <= 8 and tm >= 8 * tn), ones_col=c.ones,
+                           **fields)
+    if c.sgd is not None:
+        s = c.sgd
+        args.sgd_w, args.sgd_h, args.sgd_shadow, args.sgd_hyper = (s[k].data_ptr() for k in ("w", "h", "shadow", "hyper"))
+        args.sgd_lr_mult, args.sgd_decay_mult, args.sgd_flags = float(s["lr_mult"]), float(s["decay_mult"]), int(s["flags"])
+    return args
+
+
+def _launch(c: GemmCall, tile: int, splits: int, kchunk: int) -> None:
+    """One GEMM launch (+ the split-K reduce) with an explicit tile / split choice (``kchunk``
+    decides the split; ``splits`` is what chose it)."""
+    M, N, out = c.M, c.N, c.out
+    splits = max(1, -(-c.K // kchunk))
+    rng, dstream, ratio = c.dropout or (None, 0, 0.0)
+    dstream, ratio = int(dstream), float(ratio)
     if splits == 1:
-        e = EPI_BF16_DROP if (epi == EPI_BF16 and xtra[0]) else epi
-        lds = int(_LDS_EPI and epi == EPI_BF16 and tile in _LDS_EPI_TILES and ldc % 8 == 0 and c_gstride % 8 == 0
+        e = EPI_BF16_DROP if rng is not None else c.epi
+        lds = int(_LDS_EPI and c.epi == EPI_BF16 and tile in _LDS_EPI_TILES and c.ldc % 8 == 0 and c.c_gstride % 8 == 0
                   and out.data_ptr() % 16 == 0)
-        args = _lib.SnGemmArgs(M, N, K, groups, 1, max(kchunk, bk), a_mc, a_mode, b_mc, b_mode, e,
-                               sa, sb, out.data_ptr(), ldc, c_gstride, 0,
-                               bias.data_ptr() if bias is not None else 0, int(relu), tile, gp, f8, *dq, raster,
-                               ones, bg, int(bias_acc), *sg, *_drop_fields(xtra), lds)
+        # Philox keep threshold and the scale of what is kept
+        thr, scale = (int(4294967295 * ratio) & 0xffffffff, 1.0 / (1.0 - ratio)) if rng is not None else (0, 1.0)
+        args = _gemm_args(c, tile, splits=1, kchunk=max(kchunk, c.bk), epi=e, C=out.data_ptr(), ldc=c.ldc,
+                          c_gstride=c.c_gstride, bias=_ptr(c.bias), relu=int(c.relu), gate=_ptr(c.gate),
+                          gate_scale=c.gate_scale, bias_out=_ptr(c.bias_grad), bias_acc=int(c.bias_acc),
+                          drop_rng=_ptr(rng), drop_stream=dstream, drop_thr=thr, drop_scale=scale, lds_store=lds)
         side = _SIDE
         if side is not None and side.covers(out):
-            q = _side_fields(side, out, ldc, c_gstride, N, tile, e, lds)
+            q = _side_fields(side, c, tile, e, lds)
             if q is not None:
                 args.q_out, args.q_ld, args.q_gstride, args.q_slot, args.q_e5m2, args.q_part = q
         _lib.check(_lib.kernels().sn_gemm(C.byref(args), C.c_void_p(_lib.stream_ptr())), "gemm")
@@ -293,24 +377,22 @@ def _launch(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu, gate, bi
         _SIDE.ok = False  # the split-K reduce writes the bf16 output
     ldw = -(-N // 4) * 4  # fp32 slabs keep 16-B rows (the ones column makes N odd)
     sink = _DEFER_SINK
-    deferred = (sink is not None and epi == EPI_F32 and not fp8 and (bias_grad is None or not bias_acc)
-                and sink.accepts(out, bias_grad))
-    ws = (sink.slab(groups * splits * M * ldw, out.device).view(groups, splits, M, ldw) if deferred
-          else torch.empty((groups, splits, M, ldw), dtype=torch.float32, device=out.device))
-    args = _lib.SnGemmArgs(M, N, K, groups, splits, kchunk, a_mc, a_mode, b_mc, b_mode, EPI_F32,
-                           sa, sb, ws.data_ptr(), ldw, splits * M * ldw, M * ldw, 0, 0, tile, 0, f8, *dq, raster,
-                           ones, 0, 0, *sg, *_drop_fields(_NO_XTRA))
+    deferred = (sink is not None and c.epi == EPI_F32 and not c.fp8 and (c.bias_grad is None or not c.bias_acc)
+                and sink.accepts(out, c.bias_grad))
+    ws = (sink.slab(c.groups * splits * M * ldw, out.device).view(c.groups, splits, M, ldw) if deferred
+          else torch.empty((c.groups, splits, M, ldw), dtype=torch.float32, device=out.device))
+    args = _gemm_args(c, tile, splits=splits, kchunk=kchunk, epi=EPI_F32, C=ws.data_ptr(), ldc=ldw,
+                      c_gstride=splits * M * ldw, c_split_stride=M * ldw, drop_scale=1.0, gate_scale=1.0)
     _lib.check(_lib.kernels().sn_gemm(C.byref(args), C.c_void_p(_lib.stream_ptr())), "gemm")
     if deferred:
         # the solver update sums these slabs itself (engine.fuse_splitk_updates)
-        sink.record(dict(ws=ws, splits=splits, M=M, N=N - (1 if ones >= 0 else 0), ldw=ldw, groups=groups,
-                         ones=ones, ldc=ldc, c_gstride=c_gstride))
+        sink.record(SplitSlabs(ws, ws.data_ptr(), splits, M, N - (1 if c.ones >= 0 else 0), ldw, c.groups, c.ones,
+                               c.ldc, c.c_gstride))
         return
-    mode = {EPI_BF16: 0, EPI_F32: 1, EPI_F32_ACC: 2}[epi]
-    rng, dstream, ratio, gscale = xtra
-    _lib.call("splitk_reduce", ws, splits, M * ldw, M, N, ldw, out, ldc, mode, bias, int(relu),
-              groups, splits * M * ldw, c_gstride, gate, bias_grad, ones, int(bias_acc), M,
-              C.c_void_p(rng), int(dstream), float(ratio), float(gscale))
+    mode = {EPI_BF16: 0, EPI_F32: 1, EPI_F32_ACC: 2}[c.epi]
+    _lib.call("splitk_reduce", ws, splits, M * ldw, M, N, ldw, out, c.ldc, mode, c.bias, int(c.relu),
+              c.groups, splits * M * ldw, c.c_gstride, c.gate, c.bias_grad, c.ones, int(c.bias_acc), M,
+              C.c_void_p(_ptr(rng)), dstream, ratio, c.gate_scale)
 
 
 # --- fused fp8 side output ----------------------------------------------------------------
@@ -387,18 +469,17 @@ def fp8_side_output(side):
     side.finish()
 
 
-def _side_fields(side, out, ldc, c_gstride, N, tile, epi, lds):
-    """(q_out, q_ld, q_gstride, q_slot, q_e5m2) of one unsplit launch, or None when this
-    launch cannot store the side output (the side is then marked incomplete)."""
-    off = (out.data_ptr() - side.base.data_ptr()) // 2
+def _side_fields(side, c, tile, epi, lds):
+    """(q_out, q_ld, q_gstride, q_slot, q_e5m2, q_part) of one unsplit launch of ``c``, or None
+    when this launch cannot store the side output (the side is then marked incomplete)."""
+    off = (c.out.data_ptr() - side.base.data_ptr()) // 2
     qp = side.q.data_ptr() + off
     if ((not lds and not _SIDE_FRAG) or epi not in (EPI_BF16, EPI_BF16_DROP) or tile in (6, 7)
-            or N % 8 or ldc % 8
-            or c_gstride % 8 or qp % 8):
+            or c.N % 8 or c.ldc % 8 or c.c_gstride % 8 or qp % 8):
         side.ok = False
         return None
     side.launches += 1
-    return (qp, ldc, c_gstride, side.slot.data_ptr(), int(side.e5m2), side.part.data_ptr())
+    return (qp, c.ldc, c.c_gstride, side.slot.data_ptr(), int(side.e5m2), side.part.data_ptr())
 
 
 # --- deferred split-K reduction ---------------------------------------------------------
@@ -504,7 +585,9 @@ def _geom_key(s) -> tuple:
     return (s.ld, s.gstride) + tuple(getattr(s.g, f) for f, _ in s.g._fields_)
 
 
-def _candidates(M, N, K, groups, b_kc_dense, epi):
+def _candidates(c: GemmCall) -> list:
+    """[(tile, splits, kchunk)] worth timing for the bf16 product ``c``."""
+    M, N, K, groups, b_kc_dense, epi = c.M, c.N, c.K, c.groups, c.b_kc_dense, c.epi
     tiles = [0, 1, 2]
     if N >= 256:
         tiles.append(3)
@@ -547,7 +630,7 @@ def _candidates(M, N, K, groups, b_kc_dense, epi):
         if epi == EPI_SGD:
             continue
         for s2 in {1, 2 * s} - {s}:
-            kc2 = -(-(-(-K // s2)) // BK) * BK
+            kc2 = _kchunk(K, s2, BK)
             s2 = max(1, -(-K // kc2))
             if s2 * M * N * groups * 4 <= (256 << 20):
                 out.append((t, s2, kc2))
@@ -559,77 +642,52 @@ def _candidates(M, N, K, groups, b_kc_dense, epi):
 _FP8_TILES = (0, 11, 16)
 
 
-def _candidates_fp8(M, N, K, groups, epi, xtra, mc=False):
+def _candidates_fp8(c: GemmCall) -> list:
+    M, N, K, groups = c.M, c.N, c.K, c.groups
     out = []
-    for t in ((0,) if mc else _FP8_TILES):  # fp8 MC operands (weight gradients): 128x128 only
-        if t != 0 and (xtra[0] or epi not in (EPI_BF16, EPI_F32)):
+    for t in ((0,) if (c.a.mc or c.b.mc) else _FP8_TILES):  # fp8 MC operands (weight gradients): 128x128 only
+        if t != 0 and (c.dropout is not None or c.epi not in (EPI_BF16, EPI_F32)):
             continue
         s, kc = choose_splits(M, N, K // 2, groups, t)
         for s2 in dict.fromkeys((s, 1)):
-            kc2 = -(-(-(-K // s2)) // 128) * 128
+            kc2 = _kchunk(K, s2, 128)
             s2 = max(1, -(-K // kc2))
             if s2 == 1 or s2 * M * N * groups * 4 <= (256 << 20):  # fp32 slabs only when split
                 out.append((t, s2, kc2))
     return list(dict.fromkeys(out))
 
 
-def _tuned_config(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu, gate, bias_grad, bias_acc,
-                  ones, sg, xtra=_NO_XTRA, deq=None):
-    # (split-K caps were measured neutral or slower, docs/PERF_NOTES.md round 2; removed)
-    return _tuned_config_raw(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu, gate, bias_grad,
-                             bias_acc, ones, sg, xtra, deq)
-
-
-def _tuned_config_raw(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu, gate, bias_grad, bias_acc,
-                      ones, sg, xtra=_NO_XTRA, deq=None):
-    sa, a_mc, a_mode, sb, b_mc, b_mode = ops
-    b_kc_dense = b_mc == 0 and b_mode == OP_DENSE
-    fp8 = deq is not None
-    key = (M, N, K, groups, a_mc, a_mode, b_mc, b_mode, epi, gate is not None, bias_grad is not None, bool(xtra[0]),
-           _geom_key(sa), _geom_key(sb)) + ((("fp8",) if len(deq) < 3 or deq[2] == 1 else ("fp8", deq[2])) if fp8 else ()) + (out.dtype,)
+def _tuned_config(c: GemmCall) -> tuple[int, int, int]:
+    """(tile, splits, kchunk) of ``c``: the cached choice, else the cost model's, else (autotune
+    on, eager, on the GPU) the fastest candidate, timed now and cached."""
+    M, N, K, groups, epi, out = c.M, c.N, c.K, c.groups, c.epi, c.out
+    key = c.key
     hit = _TUNED.get(key)
     if hit is None and not _AUTOTUNE and epi != EPI_SGD:
         _MISSES.add(key)
     if hit is not None:
         return hit
-    tile = 0 if fp8 else choose_tile(M, N, b_kc_dense)
-    if epi == EPI_SGD and tile not in (0, 1, 2, 3):
-        tile = 0
-    if fp8:  # K counts e4m3 elements, 128 per K-step; the cost model counts bf16 K-steps
-        splits, kchunk = choose_splits(M, N, K // 2, groups, tile)
-        kchunk *= 2
-        splits = -(-K // kchunk)
-    else:
-        splits, kchunk = choose_splits(M, N, K, groups, tile)
-    default = (tile, splits, kchunk)
-    extent = (groups - 1) * c_gstride + (M - 1) * ldc + (N - (1 if ones >= 0 else 0))
+    default = tile, splits, _ = _model_config(c)
+    extent = (groups - 1) * c.c_gstride + (M - 1) * c.ldc + (N - (1 if c.ones >= 0 else 0))
     if (not _AUTOTUNE or epi == EPI_SGD or not out.is_cuda or torch.cuda.is_current_stream_capturing()
             or (out.is_contiguous() and extent > out.numel())):
         return default
     # a strided output (a channel slice of a zero-copy concat) is timed on a flat scratch
     scratch = torch.empty_like(out) if out.is_contiguous() else torch.empty(extent, dtype=out.dtype, device=out.device)
-    bscratch = torch.zeros_like(bias_grad) if bias_grad is not None else None
-    runs = []
-    cands = (_candidates_fp8(M, N, K, groups, epi, xtra, bool(a_mc or b_mc)) if fp8
-             else _candidates(M, N, K, groups, b_kc_dense, epi))
-    for cand in cands:
-        t, s, kc = cand
-
-        def run(t=t, s=s, kc=kc):
-            _launch(M, N, K, groups, ops, epi, scratch, ldc, c_gstride, bias, relu, gate, bscratch, bias_acc,
-                    ones, sg, t, s, kc, deq, xtra)
+    trial = replace(c, out=scratch, bias_grad=torch.zeros_like(c.bias_grad) if c.bias_grad is not None else None)
+    times = {}
+    for cand in (_candidates_fp8(c) if c.fp8 else _candidates(c)):
         try:
-            run()
+            _launch(trial, *cand)
         except RuntimeError as e:  # a tile this operand combination has no instance for
             if _TUNE_LOG:
                 print(f"[gemm-tune] candidate {cand} skipped: {e}", flush=True)
             continue
-        runs.append((cand, run))
+        times[cand] = float("inf")
     # Each candidate is timed over 4 back-to-back launches queued behind a GPU spin (so small
     # GEMMs are timed as a graph replays them, not at the host's launch rate), in 3
     # interleaved passes; the minimum per candidate counts.  A candidate must beat the cost
     # model's pick by 3% to replace it, so timing noise cannot flip a choice.
-    times = {c: float("inf") for c, _ in runs}
     # Drain every stream of the device first: inside a warm-up step with branch streams the
     # other towers' kernels would otherwise share the CUs with the candidates being timed —
     # GoogLeNet's database held choices up to 1.6x off the isolated best that way
@@ -639,12 +697,12 @@ def _tuned_config_raw(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu
     est = _cost(-(-M // TILES[tile][0]) * -(-N // TILES[tile][1]) * groups, -(-K // BK), splits, M * N * groups, tile)
     reps = max(4, min(32, int(150.0 / max(est, 1.0))))
     for _ in range(_TUNE_PASSES):
-        for cand, run in runs:
+        for cand in times:
             torch.cuda._sleep(1 << 19)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(reps):
-                run()
+                _launch(trial, *cand)
             e1.record()
             e1.synchronize()
             times[cand] = min(times[cand], e0.elapsed_time(e1))
@@ -652,9 +710,9 @@ def _tuned_config_raw(M, N, K, groups, ops, epi, out, ldc, c_gstride, bias, relu
     if default in times and times[best] > 0.97 * times[default]:
         best = default
     if _TUNE_LOG:
-        print(f"[gemm-tune] M={M} N={N} K={K} g={groups} modes={ops[1:3]}/{ops[4:]} epi={epi} "
+        print(f"[gemm-tune] M={M} N={N} K={K} g={groups} modes={(c.a.mc, c.a.mode)}/{(c.b.mc, c.b.mode)} epi={epi} "
               f"default={default} best={best} " +
-              " ".join(f"{c[0]}/{c[1]}:{v * 1000 / reps:.1f}" for c, v in sorted(times.items())), flush=True)
+              " ".join(f"{k[0]}/{k[1]}:{v * 1000 / reps:.1f}" for k, v in sorted(times.items())), flush=True)
     _TUNED[key] = best
     return best
 
@@ -730,24 +788,17 @@ def linear_dgrad(dy: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = N
         wp = torch.zeros((Np, -(-K // 8) * 8), dtype=w.dtype, device=w.device)
         wp[:N, :K].copy_(w)
     Kp = wp.shape[1]
-    if out is None or Kp != K:
-        o = torch.empty((M, Kp), dtype=torch.bfloat16, device=dy.device)
-    else:
-        o = out
-    if gate is not None and (Kp != K or not gate.is_contiguous()):
-        gemm(M, Kp, Np, Dense(dyp, Np, True), Dense(wp, Kp, False), o, o.stride(0), epi=EPI_BF16)
+    o = out if out is not None and Kp == K else torch.empty((M, Kp), dtype=torch.bfloat16, device=dy.device)
+    fused = gate is None or (Kp == K and gate.is_contiguous())  # else the gate is applied by torch
+    gemm(M, Kp, Np, Dense(dyp, Np, True), Dense(wp, Kp, False), o, o.stride(0), epi=EPI_BF16,
+         gate=gate if fused else None, gate_scale=gate_scale if fused else 1.0)
+    if not fused:
         o = o[:, :K] * (gate > 0).to(o.dtype) * gate_scale
-        if out is not None:
-            out.copy_(o)
-            return out
-        return o
-    gemm(M, Kp, Np, Dense(dyp, Np, True), Dense(wp, Kp, False), o, o.stride(0), epi=EPI_BF16, gate=gate,
-         gate_scale=gate_scale)
-    if o is not out:
+    elif o is not out:
         o = o[:, :K]
-        if out is not None:
-            out.copy_(o)
-            return out
+    if out is not None and o is not out:
+        out.copy_(o)
+        return out
     return o
 
 

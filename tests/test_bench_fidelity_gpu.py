@@ -24,6 +24,7 @@ batches, cropped / mirrored / dropped by the same Philox draws.
 
 Reference: caffe/src/caffe/test/test_gradient_based_solver.cpp:225-320 (update of one
 iteration vs a reference computed independently)."""
+import dataclasses
 import math
 
 import pytest
@@ -147,10 +148,10 @@ def test_bench_config_gate_catches_a_broken_wgrad(gpu, fixture_data, monkeypatch
     x, y, w0, uc, floor = fixture_data
     orig = G._launch
 
-    def broken(M, N, K, *a, **k):
-        if M == 96 and K >= 500000:  # conv1's folded weight gradient: 96 x 433 x 774400
-            K = K // 2
-        return orig(M, N, K, *a, **k)
+    def broken(call, *a):
+        if call.M == 96 and call.K >= 500000:  # conv1's folded weight gradient: 96 x 433 x 774400
+            call = dataclasses.replace(call, K=call.K // 2)
+        return orig(call, *a)
     monkeypatch.setattr(G, "_launch", broken)
     ug = _one_step_updates(torch.device(gpu), w0, x, y)
     bad = _violations(ug, uc, floor)

@@ -26,6 +26,8 @@ the dynamic range's, so block scales were not built into the GEMM.  The GPU land
 
 Pattern: caffe/src/caffe/test/test_gradient_based_solver.cpp:225-320 (one update against
 an independently computed one)."""
+import dataclasses
+
 import pytest
 import torch
 
@@ -174,10 +176,10 @@ def test_fp8_gate_catches_a_broken_fp8_wgrad(gpu, gate_data, monkeypatch):
     orig = G._launch
     pixels = B * (CROP // 16) ** 2
 
-    def broken(M, N, K, *a, **k):
-        if M == 512 and N in (512 * 9, 512 * 9 + 1) and K == pixels:  # (+1: the bias ones column)
-            K = K // 8
-        return orig(M, N, K, *a, **k)
+    def broken(call, *a):
+        if call.M == 512 and call.N in (512 * 9, 512 * 9 + 1) and call.K == pixels:  # (+1: the bias ones column)
+            call = dataclasses.replace(call, K=call.K // 8)
+        return orig(call, *a)
     monkeypatch.setattr(G, "_launch", broken)
     ug = _one_step(_gpu_fp8_solver(gpu, w0), x, y, w0)
     bad = _violations(ug, uc, floor)

@@ -563,3 +563,73 @@ def test_thin_tiles_bitwise_equal_at_same_split(gpu, monkeypatch):
             outs.append(torch.cat([dw.flatten(), db]))
         for o in outs[1:]:
             assert torch.equal(o, outs[0]), splits
+
+
+# --- first-call autotuning ----------------------------------------------------------------------
+
+def _fresh_tuner(monkeypatch, G, autotune):
+    monkeypatch.setattr(G, "_TUNED", {})
+    monkeypatch.setattr(G, "_MISSES", set())
+    monkeypatch.setattr(G, "_AUTOTUNE", autotune)
+
+
+def _spy(monkeypatch, G, name):
+    """Record what ``G.<name>`` returns, call by call."""
+    orig, seen = getattr(G, name), []
+
+    def spy(*a, **k):
+        seen.append(orig(*a, **k))
+        return seen[-1]
+    monkeypatch.setattr(G, name, spy)
+    return seen
+
+
+def test_first_call_autotune_dense(gpu, monkeypatch):
+    """An eager product the database lacks is timed once, on scratch: one entry, under the key a
+    miss reports, chosen among the candidates; later calls launch it once and time nothing."""
+    from sparknet_amd.ops import gemm as G
+    M, N, K = 256, 192, 512
+    x, w, b = _bf(M, K, device=gpu), _bf(N, K, device=gpu), torch.randn(N, device=gpu)
+    ref = torch.relu(x.float() @ w.float().t() + b)
+    _fresh_tuner(monkeypatch, G, False)
+    G.linear_fwd(x, w, b, relu=True)
+    (key,) = G.tune_misses()
+    _fresh_tuner(monkeypatch, G, True)
+    cands = _spy(monkeypatch, G, "_candidates")
+    y = G.linear_fwd(x, w, b, relu=True)
+    assert list(G._TUNED) == [key] and not G.tune_misses()
+    assert len(cands) == 1 and G._TUNED[key] in cands[0], (G._TUNED, cands)
+    _close(y, ref)
+    launches = _spy(monkeypatch, G, "_launch")
+    y = G.linear_fwd(x, w, b, relu=True)
+    assert len(launches) == 1 and len(cands) == 1 and list(G._TUNED) == [key]
+    _close(y, ref)
+
+
+def test_first_call_autotune_strided_output(gpu, monkeypatch):
+    """A channel slice of a wider buffer is tuned on a flat scratch: the columns outside the slice
+    are never written."""
+    from sparknet_amd.ops import gemm as G
+    M, N, K = 256, 192, 512
+    x, w, b = _bf(M, K, device=gpu), _bf(N, K, device=gpu), torch.randn(N, device=gpu)
+    buf = torch.full((M, 256), 7.0, device=gpu, dtype=torch.bfloat16)
+    out = buf[:, 32:32 + N]
+    _fresh_tuner(monkeypatch, G, True)
+    G.linear_fwd(x, w, b, relu=True, out=out)
+    assert len(G._TUNED) == 1
+    assert bool((buf[:, :32] == 7.0).all()) and bool((buf[:, 32 + N:] == 7.0).all())
+    _close(out, torch.relu(x.float() @ w.float().t() + b))
+
+
+def test_first_call_autotune_leaves_wgrad_accumulators(gpu, monkeypatch):
+    """Candidates run on scratch outputs: tuning an accumulating weight gradient with a fused bias
+    gradient adds the product to dw and db exactly once."""
+    from sparknet_amd.ops import gemm as G
+    M, N, K = 512, 64, 128
+    dy, x = _bf(M, N, device=gpu), _bf(M, K, device=gpu)
+    dw, db = torch.full((N, K), 3.0, device=gpu), torch.full((N,), -2.0, device=gpu)
+    _fresh_tuner(monkeypatch, G, True)
+    assert G.linear_wgrad(dy, x, dw, accumulate=True, db=db)
+    assert len(G._TUNED) == 1
+    _close(dw, 3.0 + dy.float().t() @ x.float(), 1e-2)
+    _close(db, -2.0 + dy.float().sum(0), 1e-3)

@@ -58,13 +58,13 @@ def test_cifar10_quick_learns_synthetic_patterns(gpu, order, monkeypatch):
     from sparknet_amd.engine import LocalSGDTrainer, fuse_relu
     from sparknet_amd.ops import gemm as G
     if order == "thin229":
-        raw = G._tuned_config_raw
+        tuned = G._tuned_config
 
-        def forced(M, N, K, *a, **k):
-            if (M, N, K) == (32, 201, 102400):  # conv1 dW + bias column over 100 x 32 x 32 pixels
+        def forced(call):
+            if (call.M, call.N, call.K) == (32, 201, 102400):  # conv1 dW + bias column over 100 x 32 x 32 pixels
                 return (22, 229, 448)
-            return raw(M, N, K, *a, **k)
-        monkeypatch.setattr(G, "_tuned_config_raw", forced)
+            return tuned(call)
+        monkeypatch.setattr(G, "_tuned_config", forced)
     mean = [125.0, 123.0, 114.0]
     x, y = _patterns(2000)
     sp = models.solver_for("cifar10_quick", train_batch=100, test_batch=100)
