@@ -42,6 +42,45 @@ __global__ void softmax_xent_fwd(const bf16_t* __restrict__ x, const float* __re
   }
 }
 
+// softmax_xent_fwd plus the input gradient of softmax_xent_bwd, for a loss whose normaliser is
+// known at launch (no ignore_label: every row is valid and norm = max(M or outer_num, 1), what
+// xent_reduce computes from M ones).  Same max / exp / sum / inv order and the same prob,
+// row_loss and row_valid stores; each lane then forms (prob - onehot) * scale from the fp32
+// prob it has just stored (the rounded value, not a recomputed or fma-contracted one) in
+// softmax_xent_bwd's expression order: dx is bitwise what the two launches give.
+__global__ void softmax_xent_fwd_bwd(const bf16_t* __restrict__ x, const float* __restrict__ labels,
+                                     float* __restrict__ prob, float* __restrict__ row_loss,
+                                     float* __restrict__ row_valid,
+                                     const float* __restrict__ loss_weight, float norm, bf16_t* __restrict__ dx,
+                                     int M, int C) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const bf16_t* xr = x + (long long)row * C;
+  float m = -INFINITY;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, bf2f(xr[c]));
+  m = wave_max(m);
+  float s = 0.f;
+  for (int c = lane; c < C; c += 64) s += __expf(bf2f(xr[c]) - m);
+  s = wave_sum(s);
+  const float inv = 1.f / s;
+  float* pr = prob + (long long)row * C;
+  bf16_t* dr = dx + (long long)row * C;
+  const int lab = (int)labels[row];
+  const float scale = loss_weight[0] / norm;
+  for (int c = lane; c < C; c += 64) {
+#pragma clang fp contract(off)  // the product is rounded to fp32 (as stored) before the subtraction: no fma
+    const float p = __expf(bf2f(xr[c]) - m) * inv;
+    pr[c] = p;
+    dr[c] = f2bf((p - (c == lab ? 1.f : 0.f)) * scale);
+  }
+  if (lane == 0) {
+    const float p = __expf(bf2f(xr[min(max(lab, 0), C - 1)]) - m) * inv;
+    row_loss[row] = -__logf(fmaxf(p, FLT_MIN_));
+    row_valid[row] = 1.f;
+  }
+}
+
 // loss = sum(row_loss) / max(norm, 1) where norm = sum(row_valid) (normalize) or outer_num
 __global__ void xent_reduce(const float* __restrict__ row_loss, const float* __restrict__ row_valid, int M,
                             int normalize, float outer_num, float* __restrict__ out_loss, float* __restrict__ out_norm) {
@@ -77,6 +116,21 @@ extern "C" int sn_softmax_xent_fwd(const bf16_t* x, const float* labels, float* 
                      labels, prob, row_loss, row_valid, (int)M, (int)C, (int)has_ignore, (int)ignore_label);
   hipLaunchKernelGGL(xent_reduce, dim3(1), dim3(1024), 0, st, row_loss, row_valid, (int)M, (int)normalize,
                      (float)outer_num, out_loss, out_norm);
+  return SN_CHECK_LAUNCH();
+}
+
+// reduce = 0: the caller sums row_loss in a later launch (the solver tail's block 0)
+extern "C" int sn_softmax_xent_fwd_bwd(const bf16_t* x, const float* labels, float* prob, float* row_loss,
+                                       float* row_valid, float* out_loss, float* out_norm, const float* loss_weight,
+                                       bf16_t* dx, long long M, long long C, long long normalize, long long outer_num,
+                                       long long reduce, hipStream_t st) {
+  const int rows_per_block = 4;
+  const float norm = fmaxf((float)(normalize ? M : outer_num), 1.f);
+  hipLaunchKernelGGL(softmax_xent_fwd_bwd, dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0,
+                     st, x, labels, prob, row_loss, row_valid, loss_weight, norm, dx, (int)M, (int)C);
+  if (reduce)
+    hipLaunchKernelGGL(xent_reduce, dim3(1), dim3(1024), 0, st, row_loss, row_valid, (int)M, (int)normalize,
+                       (float)outer_num, out_loss, out_norm);
   return SN_CHECK_LAUNCH();
 }
 

@@ -13,6 +13,7 @@
 // device memory so the launch can live in a captured hipGraph.  Gradient clipping uses
 // a deterministic two-pass sum of squares written into hyper[15].
 #include "common.h"
+#include "loss_sum.h"
 
 enum { H_LR = 0, H_MOM, H_WD, H_CLIP, H_NORM, H_DELTA, H_MOM2, H_RMS, H_CORR, H_T, H_SUMSQ = 15 };
 
@@ -251,6 +252,118 @@ extern "C" int sn_solver_update(long long kind, float* w, const float* g, float*
     case 5: launch_kind<5>(l1, clip, sh, grid, st, w, g, h0, h1, shadow, chunk_pos, chunk_mult, hyper, n, chunk_src); break;
     default: return 8;
   }
+  return SN_CHECK_LAUNCH();
+}
+
+// The tail of a captured training step in ONE launch: solver_update_kernel's SGD / Nesterov
+// arithmetic over the same chunk tables, plus the launch-bound glue around it.
+//   * gather: a chunk may read its gradient through an int32 index map instead of the flat
+//     buffer — conv1's weights read the folded dw2 of the space-to-depth weight-gradient
+//     product through the inverse of s2d_weight_grad's index map (no unfold launch);
+//   * scatter: a chunk may also store its new bf16 weights, through an int32 index map, into
+//     a derived copy — conv1's folded w2 (what s2d_weight writes; its zero padding is never
+//     touched) or a stride-1 convolution's flip-transposed wt (what flip_weights_multi
+//     writes).  The copies are pure permutations of the shadow this kernel writes, so they
+//     change exactly here;
+//   * thread 0 of block 0 bumps the Philox counter (advance_rng_kernel);
+//   * block 0 sums the row losses of a SoftmaxWithLoss head (xent_reduce, bitwise).
+// ext[4 * cid] = {gradient source address (0: the flat buffer), address of the chunk's gather
+// map, scatter target address (0: none), address of the chunk's scatter map}; a map entry
+// < 0 (the 64-element padding of a segment) means the flat gradient / no store.
+template <int KIND, bool L1>
+__global__ void __launch_bounds__(256) solver_tail_kernel(float* __restrict__ w, const float* __restrict__ g,
+                                                          float* __restrict__ h0, bf16_t* __restrict__ shadow,
+                                                          const long long* __restrict__ chunk_pos,
+                                                          const float* __restrict__ chunk_mult,
+                                                          const float* __restrict__ hyper, int nchunks,
+                                                          const long long* __restrict__ ext, long long* rng,
+                                                          const float* __restrict__ row_loss,
+                                                          const float* __restrict__ row_valid, int M, int normalize,
+                                                          float outer_num, float* __restrict__ out_loss,
+                                                          float* __restrict__ out_norm) {
+  __shared__ float ls[16], vs[16];
+  if (blockIdx.x == 0) {
+    if (rng != nullptr && threadIdx.x == 0) rng[1] += 1;
+    if (row_loss != nullptr) xent_reduce_block256(row_loss, row_valid, M, normalize, outer_num, out_loss, out_norm, ls, vs);
+  }
+  for (int cid = blockIdx.x; cid < nchunks; cid += gridDim.x) {
+  const long long start = chunk_pos[2 * cid];
+  const int count = (int)chunk_pos[2 * cid + 1];
+  const float lr_mult = chunk_mult[2 * cid], decay_mult = chunk_mult[2 * cid + 1];
+  const float rate = hyper[H_LR] * lr_mult;
+  const float mom = hyper[H_MOM];
+  const float decay = hyper[H_WD] * decay_mult;
+  const float gscale = hyper[H_NORM];
+  const float* gsrc = reinterpret_cast<const float*>(ext[4 * cid]);
+  const int* gmap = reinterpret_cast<const int*>(ext[4 * cid + 1]);
+  bf16_t* sdst = reinterpret_cast<bf16_t*>(ext[4 * cid + 2]);
+  const int* smap = reinterpret_cast<const int*>(ext[4 * cid + 3]);
+  for (int i = threadIdx.x * 4; i < count; i += blockDim.x * 4) {
+    const long long o = start + i;
+    float4 wv = *reinterpret_cast<float4*>(w + o);
+    float G[4];
+    if (gsrc == nullptr) {
+      const float4 gv = *reinterpret_cast<const float4*>(g + o);
+      G[0] = gv.x; G[1] = gv.y; G[2] = gv.z; G[3] = gv.w;
+    } else {
+      const int4 gi = *reinterpret_cast<const int4*>(gmap + i);
+      const int I[4] = {gi.x, gi.y, gi.z, gi.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) G[k] = I[k] >= 0 ? gsrc[I[k]] : g[o + k];
+    }
+    float4 a = *reinterpret_cast<float4*>(h0 + o);
+    float W[4] = {wv.x, wv.y, wv.z, wv.w};
+    float A[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float gg = G[k] * gscale;
+      gg += decay * (L1 ? ((W[k] > 0.f) - (W[k] < 0.f)) : W[k]);
+      float upd;
+      if (KIND == 0) {            // SGD
+        A[k] = mom * A[k] + rate * gg;
+        upd = A[k];
+      } else {                    // Nesterov
+        float prev = A[k];
+        A[k] = mom * A[k] + rate * gg;
+        upd = (1.f + mom) * A[k] - mom * prev;
+      }
+      W[k] -= upd;
+    }
+    *reinterpret_cast<float4*>(w + o) = make_float4(W[0], W[1], W[2], W[3]);
+    *reinterpret_cast<float4*>(h0 + o) = make_float4(A[0], A[1], A[2], A[3]);
+    *reinterpret_cast<uint2*>(shadow + o) = make_uint2(pack2(W[0], W[1]), pack2(W[2], W[3]));
+    if (sdst != nullptr) {
+      const int4 si = *reinterpret_cast<const int4*>(smap + i);
+      const int I[4] = {si.x, si.y, si.z, si.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (I[k] >= 0) sdst[I[k]] = f2bf(W[k]);
+    }
+  }
+  }
+}
+
+// kind: 0 SGD, 1 Nesterov (the fused InnerProduct update's pair); shadow is required.
+// rng / row_loss may be null (no advance / no loss sum in this launch).
+extern "C" int sn_solver_tail(long long kind, float* w, const float* g, float* h0, bf16_t* shadow,
+                              const long long* chunk_pos, const float* chunk_mult, long long nchunks,
+                              const float* hyper, long long l1, const long long* ext, long long* rng,
+                              const float* row_loss, const float* row_valid, long long M, long long normalize,
+                              long long outer_num, float* out_loss, float* out_norm, hipStream_t st) {
+  if (shadow == nullptr || ext == nullptr || (kind != 0 && kind != 1)) return 8;
+  // block 0 carries the RNG advance and the loss sum even when no chunk is left for this launch
+  dim3 grid((unsigned)(nchunks > 0 ? nchunks : 1));
+  const int n = (int)(nchunks > 0 ? nchunks : 0);
+#define SN_TAIL(KIND, L1)                                                                                       \
+  hipLaunchKernelGGL((solver_tail_kernel<KIND, L1>), grid, dim3(256), 0, st, w, g, h0, shadow, chunk_pos,       \
+                     chunk_mult, hyper, n, ext, rng, row_loss, row_valid, (int)M, (int)normalize,               \
+                     (float)outer_num, out_loss, out_norm)
+  if (kind == 0) {
+    if (l1) SN_TAIL(0, true); else SN_TAIL(0, false);
+  } else {
+    if (l1) SN_TAIL(1, true); else SN_TAIL(1, false);
+  }
+#undef SN_TAIL
   return SN_CHECK_LAUNCH();
 }
 

@@ -440,6 +440,21 @@ class Net:
         if self.flat_compute is not self.flat_data and self.flat_data is not None:
             from .. import ops
             ops.cast_f32_to_bf16(self.flat_data, self.flat_compute)
+        self.weights_changed()
+
+    weights_epoch = 0
+
+    def weights_changed(self) -> None:
+        """The weights were written outside a solver step (load, copy, broadcast, averaging):
+        copies derived from the bf16 shadow (engine.SolverTail) are stale from here on."""
+        self.weights_epoch += 1
+
+    def weights_stamp(self) -> tuple:
+        """Changes whenever the weights may have changed other than by a native solver update:
+        :meth:`weights_changed`, or an in-place torch write to the masters or the shadow (a
+        user's write through a param blob; native kernels do not bump tensor versions)."""
+        return (self.weights_epoch, self.flat_data._version if self.flat_data is not None else 0,
+                self.flat_compute._version if self.flat_compute is not None else 0)
 
     def param_segments(self) -> list[tuple[int, int, float, float]]:
         """(offset, count, lr_mult, decay_mult) per learnable (owner) param."""
@@ -486,6 +501,17 @@ class Net:
             if done.get(id(t)) != key:
                 d.fill_(w)
                 done[id(t)] = (id(d), d.data_ptr(), d._version, w)
+
+    def constant_loss_diff(self, top):
+        """The diff tensor of loss top ``top`` while it still holds the loss weight that
+        :meth:`prefill_loss_diffs` wrote (same tensor, not written since), else None."""
+        done = self.__dict__.get("_loss_diff_filled", {})
+        for t, w in self._loss_tops:
+            if t is top and t.has_diff():
+                d = t.diff
+                if done.get(id(t)) == (id(d), d.data_ptr(), d._version, w):
+                    return d
+        return None
 
     def backward_from_to(self, start: int, end: int) -> None:
         self.prefill_loss_diffs()

@@ -263,6 +263,7 @@ class Solver:
         ops.solver_update(SOLVER_KINDS[self.type], net.flat_data, net.flat_diff, self.history,
                           net.flat_compute if net.flat_compute is not net.flat_data else None,
                           tables, self.hyper, self.param.regularization_type == "L1", False, grid_limit)
+        net.weights_changed()
 
     def update_params(self) -> None:
         from .. import ops
@@ -276,6 +277,7 @@ class Solver:
         ops.solver_update(SOLVER_KINDS[self.type], net.flat_data, net.flat_diff, self.history,
                           net.flat_compute if net.flat_compute is not net.flat_data else None,
                           self._tables, self.hyper, l1, self.param.clip_gradients > 0)
+        net.weights_changed()  # (copies derived from the shadow by a captured step's tail are stale now)
 
     # -- main loop (Solver::Step) -----------------------------------------------------------
     def iteration(self):

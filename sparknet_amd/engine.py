@@ -446,6 +446,224 @@ def fuse_fc_updates(solver) -> int:
     return len(offsets)
 
 
+class _LossHead:
+    """What the SoftmaxWithLoss layers of a net need to write their input gradient in the
+    forward launch (softmax.hip softmax_xent_fwd_bwd), shared by the net's heads.  While a
+    :class:`SolverTail` is armed, the row-loss sum of ``defer_to`` (the net's single
+    unit-weight loss) is left to the tail launch: ``pending`` carries its arguments there."""
+
+    def __init__(self, net):
+        self.net = net
+        self.armed = False
+        self.defer_to = None
+        self.pending = None
+
+    def constant_weight(self, top):
+        return self.net.constant_loss_diff(top)
+
+    def take_sum(self, layer) -> bool:
+        return self.armed and self.defer_to is layer
+
+
+def fuse_loss_head(net):
+    """Let every SoftmaxWithLoss forward also write its input gradient, where its normaliser
+    is known at launch (ops.hip.loss_head_norm): the layer's backward then launches nothing.
+    Caffe runs SoftmaxLossBackwardGPU as its own pass over the probabilities
+    (softmax_loss_layer.cu:88-124); the values are bitwise those of the separate launch.
+    GPU bf16 nets only; returns the shared :class:`_LossHead`, or None."""
+    if (net.device.type != "cuda" or net.dtype == torch.float32 or net.debug_info
+            or not features.enabled("fuse_loss_head")):
+        return None
+    head = getattr(net, "_loss_head", None)
+    if head is None:
+        heads = [layer for li, layer in enumerate(net.layers)
+                 if layer.type_name == "SoftmaxWithLoss" and net.layer_need_backward[li]
+                 and net.bottom_need_backward[li][0]]
+        if not heads:
+            return None
+        head = net._loss_head = _LossHead(net)
+        for layer in heads:
+            layer.loss_head = head
+    return head
+
+
+class _TailCopies:
+    """A folded convolution's share of a :class:`SolverTail`: the folded weights it keeps
+    current and the buffer the folded weight gradient is left in, valid while it is armed."""
+
+    def __init__(self, tail, w2, dw2):
+        self.tail, self.w2, self.dw2 = tail, w2, dw2
+
+    def armed(self) -> bool:
+        return self.tail.armed
+
+
+class SolverTail:
+    """The launch-bound glue of a captured step folded into one launch (solver.hip
+    sn_solver_tail): the plain solver update of the parameters the step updates after
+    backward, reading conv1's folded weight gradient in place (no s2d_weight_grad), writing
+    the folded conv1 weights next to the bf16 shadow (no s2d_weight at the next forward),
+    advancing the Philox state and summing the loss head's row losses.  On request
+    (SN_FEATURES=solver_tail_flips=1) it also writes the flip-transposed weights of the
+    stride-1 convolutions (no flip_weights_multi at the next backward); measured slower, so
+    by default that launch stays (docs/PERF_NOTES.md, "Step tail").
+
+    The derived copies are current only while every weight change goes through this launch.
+    ``Net.weights_stamp`` moves on any other change (load, copy, broadcast, averaging, a plain
+    solver update, a user's write); :meth:`begin` then rebuilds them with the two kernels the
+    launch replaces.  Layers use the copies only between :meth:`begin` and :meth:`run`."""
+
+    def __init__(self, solver, head, plan):
+        self.solver, self.head = solver, head
+        self.folds, self.flip_batch, self.extras = plan
+        self.armed = False
+        self.stamp = None
+        self.refreshes = 0
+        self._build()
+        net = solver.net
+        if self.flip_batch is not None:
+            hooks = net.pre_backward_hooks
+            hooks[hooks.index(self.flip_batch.run)] = self._flip_unless_armed
+        for layer, w2, dw2, _ in self.folds:
+            layer.tail_copies = _TailCopies(self, w2, dw2)
+
+    @staticmethod
+    def plan(solver):
+        """(folded convs, FlipBatch, gather / scatter extras) when the tail can replace the
+        step's plain update, else None: SGD / Nesterov with L1 / L2 decay and a bf16 shadow, no
+        clipping / iter_size accumulation / gradient callbacks (Solver.overlap_eligible), no
+        split-K slab sinks, every derived copy made from an unshared weight that lives in the
+        flat buffers."""
+        from .ops import hip
+        net = solver.net
+        if (net.device.type != "cuda" or net.dtype == torch.float32 or net.debug_info
+                or not features.enabled("solver_tail") or not solver.overlap_eligible()
+                or solver.type not in ("SGD", "Nesterov") or solver.param.regularization_type not in ("L1", "L2")
+                or net.flat_compute is net.flat_data or getattr(solver, "slab_sinks", None)):
+            return None
+        users: dict = {}
+        for layer in net.layers:
+            for p in layer.params:
+                users[p.offset] = users.get(p.offset, 0) + 1
+        fused = set(getattr(solver, "fused_offsets", ()))
+
+        def own(p):  # an unshared weight of the plain update, stored in the flat buffers
+            return (p.owner is None and users.get(p.offset, 0) == 1 and p.offset not in fused
+                    and p.compute.data_ptr() == net.flat_compute.data_ptr() + 2 * p.offset and p.compute.is_contiguous())
+
+        folds, extras = [], {}
+        for li, layer in enumerate(net.layers):
+            if layer.type_name != "Convolution":
+                continue
+            s = layer.spec(net.bottom_vecs[li][0])
+            fp = hip.s2d_plan(s)
+            if fp is None:
+                continue
+            if len(net.bottom_vecs[li]) != 1 or not own(layer.weight) or hip._image_chunk(s) < s.N:
+                return None
+            f, cp, rf, sf, s2 = fp
+            w2 = torch.zeros((s.K, rf, sf, s2.C), dtype=torch.bfloat16, device=net.device)
+            dw2 = None
+            if (net.layer_need_backward[li] and layer.param_grads_needed(0) and s.Kg % 8 == 0
+                    and net._overwrite_ok().get(layer.weight.offset, False)):
+                dw2 = torch.empty((s.K, rf * sf * s2.C), dtype=torch.float32, device=net.device)
+            folds.append((layer, w2, dw2, s))
+            extras[layer.weight.offset] = (hip.s2d_unfold_map(s), dw2, w2)
+        # the flips ride along only on request: scattered through a per-element map they are 2-byte
+        # stores a cache line apart, and the launch grows by more than flip_weights_multi costs
+        # (docs/PERF_NOTES.md, "step tail"); by default that launch stays at the start of backward
+        fb = getattr(net, "_flip_batch", None) if features.enabled("solver_tail_flips") else None
+        if fb is not None:
+            if fb.run not in net.pre_backward_hooks:
+                return None
+            by_wt = {layer.flipped_weights.data_ptr(): layer for layer in net.layers
+                     if getattr(layer, "flipped_weights", None) is not None}
+            for w, wt, G, Kg, R, S, Cg in fb.items:
+                layer = by_wt.get(wt.data_ptr())
+                if layer is None or not own(layer.weight) or layer.weight.offset in extras:
+                    return None
+                extras[layer.weight.offset] = (hip.flip_map(G, Kg, R, S, Cg), None, wt)
+        return folds, fb, extras
+
+    def _build(self) -> None:
+        from .ops import hip
+        s = self.solver
+        fused = set(getattr(s, "fused_offsets", ()))
+        segs = [sg for sg in s.net.param_segments() if sg[0] not in fused]
+        self.tables = hip.solver_tail_tables(segs, s.net.num_param_elems, s.device, self.extras)
+        self._fused = fused
+
+    def _flip_unless_armed(self) -> None:
+        if not self.armed:
+            self.flip_batch.run()
+
+    def stale(self) -> bool:
+        return self.stamp != self.solver.net.weights_stamp()
+
+    def refresh(self) -> None:
+        """Rebuild the derived copies from the shadow with the kernels the tail replaces."""
+        from .ops import hip
+        for layer, w2, _, s in self.folds:
+            f, cp, rf, sf, _ = hip.s2d_plan(s)
+            hip.call("s2d_weight", layer.weight.compute, w2, s.K, s.R, s.S, s.C, f, cp, rf, sf)
+        if self.flip_batch is not None:
+            self.flip_batch.run()
+        self.stamp = self.solver.net.weights_stamp()
+        self.refreshes += 1
+
+    def begin(self) -> None:
+        """Before the step's forward: make the copies current and let the layers use them."""
+        if ([x.data_ptr() for x in self.tables["held"]] != self.tables["ptrs"]
+                or set(getattr(self.solver, "fused_offsets", ())) != self._fused):
+            assert not torch.cuda.is_current_stream_capturing(), "solver tail tables changed during capture"
+            self._build()
+        if self.stale():
+            self.refresh()
+        self.armed = True
+        self.head_armed(True)
+
+    def head_armed(self, on: bool) -> None:
+        if self.head is not None:
+            self.head.armed = on
+            if not on:
+                self.head.pending = None
+
+    def run(self) -> None:
+        """After backward: the tail launch (in place of advance_rng + Solver.update_params)."""
+        from .ops import hip
+        from .core.solver import SOLVER_KINDS
+        s, net = self.solver, self.solver.net
+        loss = self.head.pending if self.head is not None else None
+        hip.solver_tail(SOLVER_KINDS[s.type], net.flat_data, net.flat_diff, s.history, net.flat_compute, self.tables,
+                        s.hyper, s.param.regularization_type == "L1", net.ctx.rng_state, loss)
+        self.armed = False
+        self.head_armed(False)
+        self.stamp = net.weights_stamp()
+
+    def abort(self) -> None:
+        self.armed = False
+        self.head_armed(False)
+        self.stamp = None
+
+
+def solver_tail(solver):
+    """A :class:`SolverTail` for the solver's captured step (see its ``plan``), or None."""
+    plan = SolverTail.plan(solver)
+    if plan is None:
+        return None
+    head = fuse_loss_head(solver.net)
+    if head is not None:
+        net = solver.net
+        tops = net._loss_tops
+        heads = [(li, layer) for li, layer in enumerate(net.layers) if getattr(layer, "loss_head", None) is head] \
+            if len(tops) == 1 and tops[0][1] == 1.0 else []
+        # the loss read back is that one head's scalar (Net.loss_value returns its tensor):
+        # the sum can wait for the end of the step
+        if len(heads) == 1 and net.top_vecs[heads[0][0]][0] is tops[0][0]:
+            head.defer_to = heads[0][1]
+    return SolverTail(solver, head, plan)
+
+
 class _SlabGrad:
     """Split-K slabs of one Convolution's weight gradient (and its bias column) left for
     the solver: the update kernel sums them in split order per parameter (solver.hip
@@ -1012,6 +1230,11 @@ class GraphStep:
         elif fuse_fc:
             fuse_fc_updates(solver)
             fuse_splitk_updates(solver)
+        # the loss head writes its input gradient in its forward launch; with the in-layer
+        # updates above, what is left after backward is one tail launch (SolverTail)
+        self.tail = solver_tail(solver) if (fuse_fc and self.overlap is None) else None
+        if self.tail is None and features.enabled("loss_head_without_tail"):
+            fuse_loss_head(solver.net)  # on its own it removes one launch: measured no gain, opt-in
         # parallel Inception towers etc.; built lazily, used from the 2nd warmup iteration
         # on (the first one autotunes GEMMs, timed on an otherwise idle GPU).  Two
         # streams by default; more use the star topology (see BranchStreams)
@@ -1034,12 +1257,23 @@ class GraphStep:
             self.overlap.begin()
         if self._use_branches and self.branches is None:
             self.branches = branch_streams(net, self.n_streams) or False
-        loss = (self.branches.forward_backward() if self._use_branches and self.branches
-                else net.forward_backward())
-        net.finish_param_diffs()
-        fp8_step(net)
-        for cb in s.callbacks:
-            getattr(cb, "on_gradients_ready", lambda: None)()
+        tail = self.tail
+        if tail is not None:
+            tail.begin()  # derived weight copies current; the layers skip the fold / unfold / flips
+        try:
+            loss = (self.branches.forward_backward() if self._use_branches and self.branches
+                    else net.forward_backward())
+            net.finish_param_diffs()
+            fp8_step(net)
+            for cb in s.callbacks:
+                getattr(cb, "on_gradients_ready", lambda: None)()
+            if tail is not None:
+                tail.run()  # Philox advance + update + loss sum, one launch
+                return loss
+        except BaseException:
+            if tail is not None:
+                tail.abort()
+            raise
         ops.advance_rng(net.ctx.rng_state)
         if self.overlap is not None:
             self.overlap.end()
@@ -1108,6 +1342,8 @@ class GraphStep:
         if self.pre:
             self.pre()
         s.stage_hyper()
+        if self.tail is not None and self.tail.stale():
+            self.tail.refresh()  # the weights changed outside the step: rebuild the copies the replay reads
         self.graph.replay()
         s.iter += 1
         if d > 0:

@@ -149,8 +149,29 @@ class SoftmaxWithLossLayer(LossLayer):
         if len(tops) > 1:
             tops[1].reshape(b.shape, self.dtype)
 
+    loss_head = None  # engine.fuse_loss_head: the forward launch also writes the input gradient
+    _dx = None        # that gradient, with the loss-weight tensor (and its version) it was scaled by
+
     def forward(self, bottoms, tops):
         x2 = rows_view(bottoms[0], self.axis)
+        self._dx = None
+        head = self.loss_head
+        if head is not None and x2.is_cuda:
+            # the top's diff while it holds the constant loss weight the net wrote (else None)
+            lw = head.constant_weight(tops[0])
+            from ..ops import hip
+            if hip.loss_head_norm(x2.shape[0], self.outer, self.ignore_label, self.normalize, lw is not None) is not None:
+                defer = head.take_sum(self)
+                loss, prob, norm, dx, rows = hip.softmax_loss_forward_backward(
+                    x2, bottoms[1].data, lw, self.normalize, self.outer, reduce=not defer)
+                if defer:  # the row losses are summed by the step's tail launch (engine.SolverTail)
+                    head.pending = (rows, x2.shape[0], bool(self.normalize), self.outer, loss, norm)
+                self._dx = (dx, lw, lw._version)
+                self.prob, self.norm = prob, norm
+                tops[0].data = loss.reshape(())
+                if len(tops) > 1:
+                    tops[1].data = rows_view_back(prob, bottoms[0], self.axis).to(self.dtype)
+                return
         loss, prob, norm = ops.softmax_loss_forward(x2, bottoms[1].data, self.ignore_label,
                                                     self.normalize, self.outer)
         self.prob, self.norm = prob, norm
@@ -161,9 +182,13 @@ class SoftmaxWithLossLayer(LossLayer):
     def backward(self, tops, propagate_down, bottoms):
         if len(propagate_down) > 1 and propagate_down[1]:
             raise ValueError("SoftmaxWithLoss cannot backpropagate to label inputs")
+        fused, self._dx = self._dx, None
         if propagate_down[0]:
-            g = ops.softmax_loss_backward(self.prob, bottoms[1].data, tops[0].diff, self.norm,
-                                          self.ignore_label, bottoms[0].dtype)
+            if fused is not None and tops[0].diff is fused[1] and fused[1]._version == fused[2]:
+                g = fused[0]  # written by this pass's forward with the loss weight still in place: no launch
+            else:
+                g = ops.softmax_loss_backward(self.prob, bottoms[1].data, tops[0].diff, self.norm,
+                                              self.ignore_label, bottoms[0].dtype)
             bottoms[0].diff = rows_view_back(g, bottoms[0], self.axis).to(bottoms[0].dtype)
 
 

@@ -236,6 +236,7 @@ class ConvolutionLayer(Layer):
     folded_input = None  # S2D-folded bottom 0 written by a fused augment (engine.fuse_input_fold)
     concat_slot = None  # (ConcatSlots, part): top 0 is written into a zero-copy Concat buffer (engine.fuse_concat)
     flipped_weights = None  # dgrad weights flipped at the start of backward (engine.batch_weight_flips)
+    tail_copies = None  # folded weights / folded weight gradient kept by the step's tail launch (engine.SolverTail)
 
     def layer_setup(self, bottoms, tops):
         cp = self.lp.convolution_param
@@ -280,6 +281,9 @@ class ConvolutionLayer(Layer):
         bias = self.bias.data if self.bias is not None else None
         from ..ops.hip import ConvScratch
         self._ws = [ConvScratch() for _ in bottoms]  # forward -> backward scratch (e.g. folded input)
+        tc = self.tail_copies
+        if tc is not None and tc.armed():
+            self._ws[0].w2 = tc.w2  # kept current by the step's tail launch: no fold here
         for i, (b, t) in enumerate(zip(bottoms, tops)):
             s = self.spec(b)
             side = self._fp8_out_side(s) if i == 0 else None
@@ -391,6 +395,12 @@ class ConvolutionLayer(Layer):
                                   self._side_part("bwd", t.diff.device))
             dw_acc = not (dw is not None and self.grad_overwrite(0))
             db_acc = not (db is not None and self.grad_overwrite(1))
+            tc = self.tail_copies
+            if tc is not None and tc.dw2 is not None and tc.armed():
+                if dw is None or dw_acc or len(bottoms) != 1:
+                    raise RuntimeError(f"{self.name}: the solver tail reads this layer's folded weight gradient, "
+                                       "which must be written once per step")
+                ws.dw2 = tc.dw2  # the tail launch unfolds it through its gather map
             sink = getattr(self, "slab_grad", None)
             if sink is not None and dw is not None and not dw_acc and not (db is not None and db_acc):
                 # engine.fuse_splitk_updates: the solver sums this product's split-K slabs

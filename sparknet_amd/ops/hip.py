@@ -204,8 +204,12 @@ def conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=Non
     plan = _s2d_plan(s)
     if plan is not None:
         f, cp, rf, sf, s2 = plan
-        w2 = torch.empty((s.K, rf, sf, s2.C), dtype=BF16, device=x.device)
-        call("s2d_weight", _c(w), w2, s.K, s.R, s.S, s.C, f, cp, rf, sf)
+        w2 = ws.w2 if ws is not None else None
+        if w2 is None:
+            w2 = torch.empty((s.K, rf, sf, s2.C), dtype=BF16, device=x.device)
+            call("s2d_weight", _c(w), w2, s.K, s.R, s.S, s.C, f, cp, rf, sf)
+        else:
+            assert tuple(w2.shape) == (s.K, rf, sf, s2.C) and w2.dtype == BF16 and w2.is_contiguous()
         x2 = folded if folded is not None else _s2d_input(x, s, plan)
         if ws is not None:
             ws.s2d = (x.data_ptr(), x._version, x2)
@@ -418,6 +422,10 @@ class ConvScratch:
     s2d_full: tuple | None = None
     # set by the layer before each conv_backward
     wt: torch.Tensor | None = None       # the flip-transposed weights (FlipBatch)
+    # set by the layer before conv_forward / conv_backward while the step's tail launch keeps the
+    # space-to-depth copies (engine.SolverTail); None: fold / unfold here as usual
+    w2: torch.Tensor | None = None       # the folded weights, current: conv_forward launches no s2d_weight
+    dw2: torch.Tensor | None = None      # leave the folded weight gradient here: no s2d_weight_grad launch
     fp8_dgrad: Fp8Dgrad | None = None
     fp8_wgrad: Fp8Wgrad | None = None
     fp8_dx_side: tuple | None = None     # (slot, e5m2, part): store dx as fp8 too; conv_backward takes it
@@ -559,10 +567,15 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
         if x2 is None:
             x2 = _s2d_input(x, s, plan)
         k2 = rf * sf * s2.C
-        dw2 = torch.empty((s.K, k2), dtype=torch.float32, device=x.device)
+        keep = ws.dw2  # the solver tail reads the folded gradient through its gather map
+        if keep is not None:
+            assert not dw_acc, "a folded weight gradient left for the solver tail cannot accumulate"
+            assert tuple(keep.shape) == (s.K, k2) and keep.dtype == torch.float32 and keep.is_contiguous()
+        dw2 = keep if keep is not None else torch.empty((s.K, k2), dtype=torch.float32, device=x.device)
         gemm(s.K, k2, M, Dense(dy2, s.K, kcontig=False), Im2col(x2, _geom(s2), kcontig=False), dw2, k2,
              epi=EPI_F32, bias_grad=db if fused_db else None, bias_acc=db_acc)
-        call("s2d_weight_grad", dw2, dw, s.K, s.R, s.S, s.C, f, cp, rf, sf, int(dw_acc))
+        if keep is None:
+            call("s2d_weight_grad", dw2, dw, s.K, s.R, s.S, s.C, f, cp, rf, sf, int(dw_acc))
         dw = None
     if dw is not None:
         if _wgrad_implicit_ok(s):
@@ -1166,6 +1179,43 @@ def softmax_loss_forward(x2, labels, ignore_label=None, normalize=True, outer_nu
     return out[0], prob, out[1:2]
 
 
+def loss_head_norm(M: int, outer_num, ignore_label, normalize, weight_is_constant: bool):
+    """The normaliser of a SoftmaxWithLoss whose forward may also write its input gradient
+    (softmax_xent_fwd_bwd), or None where it may not.  The gradient's scale, loss_weight /
+    norm, must be known at launch: without ``ignore_label`` every row is valid, so the count
+    xent_reduce sums (``normalize``) is M and norm = max(M or outer_num, 1), exact in fp32
+    below 2^24.  With ``ignore_label`` the valid count (normalize) and the rows to zero are
+    data; a loss weight that is not the constant the net wrote into the top's diff at set-up
+    (Net.prefill_loss_diffs) may change between the forward and the backward."""
+    if ignore_label is not None or not weight_is_constant:
+        return None
+    n = int(M) if normalize else int(outer_num if outer_num is not None else M)
+    if not (0 < int(M) < (1 << 24) and n < (1 << 24)):
+        return None
+    return float(max(n, 1))
+
+
+def softmax_loss_forward_backward(x2, labels, loss_weight, normalize=True, outer_num=None, reduce=True):
+    """softmax_loss_forward plus the input gradient in the same launch, where
+    :func:`loss_head_norm` allows it (no ignore_label).  ``loss_weight``: the device scalar
+    the gradient is scaled by (the loss top's diff).  ``reduce`` False leaves the row-loss
+    sum to a later launch (:func:`solver_tail`): returns the rows buffer for it.
+    Returns (loss, prob, norm, dx, rows)."""
+    x2 = as_bf16(x2)
+    M, Cn = x2.shape
+    dev = x2.device
+    prob = torch.empty((M, Cn), dtype=torch.float32, device=dev)
+    rows = torch.empty((2, M), dtype=torch.float32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    dx = torch.empty((M, Cn), dtype=BF16, device=dev)
+    lab = _c(labels.reshape(-1).float())
+    lw = loss_weight.reshape(-1)
+    assert lw.dtype == torch.float32 and lw.numel() >= 1
+    call("softmax_xent_fwd_bwd", x2, lab, prob, rows[0], rows[1], out[0:1], out[1:2], lw, dx, M, Cn,
+         int(normalize), int(outer_num if outer_num is not None else M), int(reduce))
+    return out[0], prob, out[1:2], dx, rows
+
+
 def softmax_loss_backward(prob, labels, loss_weight, norm, ignore_label=None, dtype=BF16):
     M, Cn = prob.shape
     dx = torch.empty((M, Cn), dtype=BF16, device=prob.device)
@@ -1243,6 +1293,106 @@ def solver_update(kind, data, diff, history, compute, tables, hyper, l1, clip, g
     call("solver_update", int(kind), data, diff, h0, h1, compute, tables["pos"], tables["mult"], tables["n"],
          hyper, int(l1), int(clip), tables["part"], tables["part"].numel(), tables["total"], int(grid_limit),
          tables.get("src"))
+
+
+def s2d_fold_map(s: ConvSpec) -> torch.Tensor:
+    """s2d_weight's index map (host, int32): element j of the folded weights [K][Rf][Sf][f*f*Cp]
+    is element map[j] of the weights [K][R][S][C], or zero padding where map[j] < 0."""
+    f, cp, rf, sf, s2 = _s2d_plan(s)
+    c2 = f * f * cp
+    j = torch.arange(s.K * rf * sf * c2, dtype=torch.int64)
+    cc, t = j % c2, j // c2
+    sfi, t = t % sf, t // sf
+    rfi, k = t % rf, t // rf
+    c, d = cc % cp, cc // cp
+    r, ss = rfi * f + d // f, sfi * f + d % f
+    src = ((k * s.R + r) * s.S + ss) * s.C + c
+    return torch.where((r < s.R) & (ss < s.S) & (c < s.C), src, torch.full_like(src, -1)).to(torch.int32)
+
+
+def s2d_unfold_map(s: ConvSpec) -> torch.Tensor:
+    """s2d_weight_grad's index map (host, int32): element i of [K][R][S][C] is element map[i] of
+    the folded [K][Rf][Sf][f*f*Cp] tensor — the inverse of :func:`s2d_fold_map` off its padding."""
+    f, cp, rf, sf, s2 = _s2d_plan(s)
+    i = torch.arange(s.K * s.R * s.S * s.C, dtype=torch.int64)
+    c, t = i % s.C, i // s.C
+    ss, t = t % s.S, t // s.S
+    r, k = t % s.R, t // s.R
+    dst = ((k * rf + r // f) * sf + ss // f) * (f * f * cp) + ((r % f) * f + ss % f) * cp + c
+    return dst.to(torch.int32)
+
+
+def flip_map(G: int, Kg: int, R: int, S: int, Cg: int) -> torch.Tensor:
+    """flip_weights_multi's index map (host, int32): element i of W [G][Kg][R][S][Cg] goes to
+    element map[i] of Wt [G][Cg][R][S][Kg], taps reversed."""
+    rs = R * S
+    i = torch.arange(G * Kg * rs * Cg, dtype=torch.int64)
+    c, t = i % Cg, i // Cg
+    tap, t = t % rs, t // rs
+    k, g = t % Kg, t // Kg
+    return (((g * Cg + c) * rs + (rs - 1 - tap)) * Kg + k).to(torch.int32)
+
+
+MAP_CHUNK = 1024  # chunk of a segment with a gather / scatter map: one pass of the block, a short dependent-load chain
+
+
+def solver_tail_tables(segments, total: int, device, extras=None) -> dict:
+    """Chunk table of the tail launch: :func:`solver_tables`' (start, count, lr_mult,
+    decay_mult) chunks plus per-chunk gather / scatter descriptors.
+    ``extras``: {segment offset: (map, gather source or None, scatter target or None)} with
+    ``map`` the host int32 index of every element of the segment in those tensors (conv1:
+    :func:`s2d_unfold_map` into the folded weight gradient and the folded weights; a stride-1
+    conv: :func:`flip_map` into its flip-transposed weights).  Mapped segments are cut into
+    MAP_CHUNK-element chunks (the update is per element: the chunking does not change a bit).
+    The descriptors hold raw device addresses: ``ptrs`` lists the tensors they were built from."""
+    extras = extras or {}
+    pos, mult, maps, ext, held, at = [], [], [], [], [], 0
+    for off, cnt, lm, dm in segments:
+        padded = -(-cnt // 64) * 64
+        e = extras.get(off)
+        if e is None:
+            for s in range(0, padded, CHUNK):
+                pos.append((off + s, min(CHUNK, padded - s)))
+                mult.append((lm, dm))
+                ext.append((None, 0, None, 0))
+            continue
+        m, gsrc, sdst = e
+        assert m.dtype == torch.int32 and m.numel() == cnt and int(m.min()) >= 0
+        for tsr, dt in ((gsrc, torch.float32), (sdst, BF16)):
+            assert tsr is None or (tsr.is_contiguous() and tsr.dtype == dt and int(m.max()) < tsr.numel())
+        mp = torch.full((padded,), -1, dtype=torch.int32)
+        mp[:cnt] = m
+        maps.append(mp)
+        for s in range(0, padded, MAP_CHUNK):
+            pos.append((off + s, min(MAP_CHUNK, padded - s)))
+            mult.append((lm, dm))
+            ext.append((gsrc, at + s, sdst, at + s))
+        at += padded
+        held += [x for x in (gsrc, sdst) if x is not None]
+    t = {"pos": torch.tensor(pos or [(0, 0)], dtype=torch.int64, device=device),
+         "mult": torch.tensor(mult or [(0.0, 0.0)], dtype=torch.float32, device=device),
+         "n": len(pos), "total": total}
+    dev_maps = (torch.cat(maps) if maps else torch.zeros(4, dtype=torch.int32)).to(device)
+    base = dev_maps.data_ptr()
+    rows = [(0 if g is None else g.data_ptr(), 0 if g is None else base + 4 * gm,
+             0 if d is None else d.data_ptr(), 0 if d is None else base + 4 * dm) for g, gm, d, dm in ext]
+    t["ext"] = torch.tensor(rows or [(0, 0, 0, 0)], dtype=torch.int64, device=device)
+    t["maps"] = dev_maps
+    t["held"] = held
+    t["ptrs"] = [x.data_ptr() for x in held]
+    return t
+
+
+def solver_tail(kind, data, diff, history, compute, tables, hyper, l1, rng_state=None, loss=None):
+    """The step's tail in one launch (sn_solver_tail): the plain SGD / Nesterov update of
+    ``tables`` (:func:`solver_tail_tables`) with its gathers and scatters, the Philox advance of
+    ``rng_state`` and the row-loss sum ``loss`` = (rows [2, M], M, normalize, outer_num, out_loss,
+    out_norm) of a fused loss head (softmax_loss_forward_backward(reduce=False))."""
+    assert int(kind) in (0, 1) and compute is not None
+    rows, M, normalize, outer, out_loss, out_norm = loss if loss is not None else (None, 0, False, 0, None, None)
+    call("solver_tail", int(kind), data, diff, history[0], compute, tables["pos"], tables["mult"], tables["n"],
+         hyper, int(l1), tables["ext"], rng_state, None if rows is None else rows[0], None if rows is None else rows[1],
+         int(M), int(bool(normalize)), int(outer if outer is not None else M), out_loss, out_norm)
 
 
 def scale_shadow(flat, shadow, scale: float):

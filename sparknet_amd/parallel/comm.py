@@ -204,6 +204,7 @@ class Comm:
             _scale(flat[s:e], shadow[s:e] if shadow is not None else None, scale)
         if not cuda:
             net.sync_compute()
+        net.weights_changed()  # (the scale kernel refreshed the shadow; copies derived from it are stale)
         return t
 
     def allreduce_grads(self, net, average: bool = True) -> None:

@@ -23,6 +23,10 @@ DEFAULTS = {
     "fuse_bn_scale": True,      # BatchNorm -> Scale -> ReLU chains in the fused per-channel kernels
     "branch_depfree": True,     # dependency-free backward nodes on the least recently used stream
     "fuse_splitk": False,       # solver update sums split-K slabs (measured slower, opt-in)
+    "fuse_loss_head": True,     # captured step with the tail launch: SoftmaxWithLoss forward also writes its input gradient
+    "loss_head_without_tail": False,  # ... also where the tail is off or not eligible (alone: measured no gain, opt-in)
+    "solver_tail": True,        # captured step: update + conv1 weight fold / unfold + RNG advance + loss sum in one launch
+    "solver_tail_flips": False,  # ... and the dgrad weight flips (2-byte scattered stores: measured slower, opt-in)
     # convolution kernel selection (ops/hip.py)
     "conv_direct_c64": True,    # LDS-resident direct 3x3 conv, 64 -> 64 channels
     "conv_direct_k96": True,    # the same kernel at 96 outputs (AlexNet conv1 after the fold)
