@@ -12,6 +12,8 @@
 * ``resnet_cifar``   — not in the reference; the 6n+2-layer CIFAR ResNet from the same constructors
 * ``mobilenet``      — not in the reference; the public Caffe MobileNet v1 layout (depthwise 3x3 +
   pointwise 1x1 blocks, each conv followed by BatchNorm -> Scale -> ReLU)
+* ``resnext50``      — not in the reference; ResNeXt-50 32x4d (Xie et al. 2017): ResNet-50's stem and
+  head around bottlenecks whose 3x3 is a 32-group convolution carrying the stage's stride
 
 Each builder returns a NetParameter whose data entry points are SparkNet ``JavaData``
 layers (TRAIN and TEST variants, like ProtoLoader.replaceDataLayers), and each has a
@@ -342,6 +344,45 @@ def mobilenet(train_batch=32, test_batch=50, crop=224, classes=1000, alpha=1.0):
     return NetParam("MobileNet", *L)
 
 
+def _resnext_block(L, tag, bottom, width, cardinality, stride, project):
+    """res{tag}: 1x1 -> grouped 3x3 (stride, ``cardinality`` groups: csrc/kernels/conv_grouped.hip)
+    -> 1x1 (x2), summed with the input or its projection."""
+    short = bottom
+    if project:
+        short = _conv_bn(L, f"res{tag}_branch1", f"{tag}_branch1", bottom, 1, 2 * width, stride=stride, relu=False)
+    x = _conv_bn(L, f"res{tag}_branch2a", f"{tag}_branch2a", bottom, 1, width)
+    x = _conv_bn(L, f"res{tag}_branch2b", f"{tag}_branch2b", x, 3, width, stride=stride, pad=1, group=cardinality)
+    x = _conv_bn(L, f"res{tag}_branch2c", f"{tag}_branch2c", x, 1, 2 * width, relu=False)
+    L += [EltwiseLayer(f"res{tag}", [short, x], "SUM"), _relu(f"res{tag}_relu", f"res{tag}")]
+    return f"res{tag}"
+
+
+def resnext(reps=(3, 4, 6, 3), cardinality=32, width=4, train_batch=32, test_batch=50, crop=224, classes=1000):
+    """ResNeXt (Xie et al. 2017, "Aggregated Residual Transformations") in ResNet-50's layout and
+    layer names: not in the reference.  Stage ``s`` (2..5) has ``reps[s - 2]`` bottlenecks of
+    1x1 to D = cardinality * width * 2^(s - 2), a 3x3 with ``cardinality`` groups D -> D that
+    carries the stage's stride, and 1x1 to 2 D; projection shortcuts where the shape changes.
+    The defaults are ResNeXt-50 32x4d: 25 028 904 learnable elements besides the BatchNorm
+    statistics."""
+    L = list(data_layers(train_batch, test_batch, 3, crop, crop))
+    x = _conv_bn(L, "conv1", "_conv1", "data", 7, 64, stride=2, pad=3)
+    L.append(_pool("pool1", x, 3, 2))
+    x = "pool1"
+    for stage, n in enumerate(reps, 2):
+        d = cardinality * width * 2 ** (stage - 2)
+        for r in range(n):
+            x = _resnext_block(L, f"{stage}{chr(ord('a') + r)}", x, d, cardinality,
+                               2 if (r == 0 and stage > 2) else 1, r == 0)
+    L += [PoolingLayer("pool5", [x], Pooling.Ave, global_pooling=True),
+          _ip(f"fc{classes}", "pool5", classes, MSRA, _c(0.0)), *_head(f"fc{classes}", top5=True)]
+    return NetParam("ResNeXt", *L)
+
+
+def resnext50(train_batch=32, test_batch=50, crop=224, classes=1000):
+    """ResNeXt-50 32x4d: :func:`resnext` at its defaults."""
+    return resnext(train_batch=train_batch, test_batch=test_batch, crop=crop, classes=classes)
+
+
 # --- solvers ------------------------------------------------------------------------------
 
 def _solver(net, **kw):
@@ -405,12 +446,18 @@ def mobilenet_solver(net=None):
                    display=20, max_iter=500000, momentum=0.9, weight_decay=4e-5)
 
 
+def resnext50_solver(net=None):  # ResNet-50's schedule
+    return _solver(net or resnext50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
+                   gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
+
+
 MODELS = {
     "lenet": (lenet, lenet_solver), "cifar10_quick": (cifar10_quick, cifar10_quick_solver),
     "cifar10_full": (cifar10_full, cifar10_full_solver), "caffenet": (caffenet, caffenet_solver),
     "alexnet": (alexnet, alexnet_solver), "googlenet": (googlenet, googlenet_solver),
     "vgg16": (vgg16, vgg16_solver), "resnet50": (resnet50, resnet50_solver),
     "resnet_cifar": (resnet_cifar, resnet_cifar_solver), "mobilenet": (mobilenet, mobilenet_solver),
+    "resnext50": (resnext50, resnext50_solver),
 }
 
 

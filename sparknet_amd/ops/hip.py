@@ -254,6 +254,9 @@ def conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=Non
     if direct_io and ldy == s.K and depthwise_ok(s) and _dw_io_ok(x, w, y):
         call("conv_dw_fwd", x, w, b, y, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw, int(relu))
         return y
+    if direct_io and ldy == s.K and grouped_ok(s) and _dw_io_ok(x, w, y):
+        call(GROUPED_FWD, x, w, b, y, s.N, s.H, s.W, s.C, s.Cg, s.sh, s.sw, s.ph, s.pw, int(relu))
+        return y
     if _implicit_ok(s):
         kred = s.R * s.S * s.Cg
         A = Im2col(x, _geom(s, ldx), kcontig=True, gstride=s.Cg)
@@ -379,6 +382,33 @@ def _dw_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
     n = int(k.sn_conv_dw_part_floats(*(C.c_longlong(v) for v in (s.N, s.P, s.Q, s.C))))
     if n <= 0:
         raise ValueError(f"depthwise weight gradient: unsupported geometry {s}")
+    return torch.empty(n, dtype=torch.float32, device=device), n
+
+
+GROUPED_WIDTHS = (4, 8, 16)  # channels per group the narrow-group kernels are routed for
+_GROUPED_MAX_PIX = 1 << 30  # pixels of a tensor per launch
+GROUPED_FWD, GROUPED_WGRAD, GROUPED_DGRAD = "conv_grouped_fwd", "conv_grouped_wgrad", "conv_grouped_dgrad"
+
+
+def grouped_ok(s: ConvSpec) -> bool:
+    """Narrow-group 3x3 convolutions the bundle kernels take (csrc/kernels/conv_grouped.hip):
+    as many outputs as inputs per group (1 < Cg == Kg, a routed width), whole 16-channel bundles,
+    strides 1 or 2 per axis, no dilation, inside the limits of the kernels' 32-bit pixel
+    arithmetic (sn_conv_grouped_*'s geometry check).  Everything else — Cg != Kg, other windows,
+    C % 16 != 0 — keeps the implicit grouped GEMM or the per-group path.  The switch is read on
+    every call (SN_FEATURES=conv_grouped=0)."""
+    return (1 < s.Cg == s.Kg and s.Cg in GROUPED_WIDTHS and s.C % 16 == 0 and s.R == 3 and s.S == 3
+            and s.dh == 1 and s.dw == 1 and s.sh in (1, 2) and s.sw in (1, 2)
+            and max(s.N * s.H * s.W, s.N * s.P * s.Q) < _GROUPED_MAX_PIX and s.P > 0 and s.Q > 0
+            and max(s.C, s.ph, s.pw) <= 1 << 20 and features.enabled("conv_grouped"))
+
+
+def _grouped_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
+    k = _lib.kernels()
+    k.sn_conv_grouped_part_floats.restype = C.c_longlong
+    n = int(k.sn_conv_grouped_part_floats(*(C.c_longlong(v) for v in (s.N, s.P, s.Q, s.C, s.Cg))))
+    if n <= 0:
+        raise ValueError(f"grouped weight gradient: unsupported geometry {s}")
     return torch.empty(n, dtype=torch.float32, device=device), n
 
 
@@ -558,6 +588,14 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
         call("conv_dw_wgrad", dy2, x, part, n, dw, 0 if dw is None else 1 + int(dw_acc),
              db, 0 if db is None else 1 + int(db_acc), s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
         return
+    if dw is not None and plan is None and ldd == s.K and ldx == s.C and grouped_ok(s) and _dw_io_ok(dy2, x):
+        # per-bundle tap products over slabs of pixels, fixed-order finalize; the bias gradient
+        # stays a column sum
+        if db is not None:
+            colsum(dy2, db, accumulate=db_acc)
+        part, n = _grouped_part(s, x.device)
+        call(GROUPED_WGRAD, dy2, x, part, n, dw, int(dw_acc), s.N, s.H, s.W, s.C, s.Cg, s.sh, s.sw, s.ph, s.pw)
+        return
     if db is not None and not fused_db:
         assert ldd == s.K
         colsum(dy2, db, accumulate=db_acc)
@@ -691,6 +729,10 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out):
     fp8 = flip and ws.fp8_dgrad is not None and fp8_dgrad_ok(s) and ldd == s.K
     if _dy_fp8_only(ws) and not fp8:
         _no_bf16_dy("a bf16 data gradient")
+    if (ldd == s.K and grouped_ok(s) and ws.fp8_dgrad is None and _dw_io_ok(dy, w, dx, gate)
+            and not _side_covers(dx)):
+        call(GROUPED_DGRAD, dy, w, gate, dx, s.N, s.H, s.W, s.C, s.Cg, s.sh, s.sw, s.ph, s.pw)
+        return dx
     if flip:
         # dgrad == forward conv of dy with flipped / transposed weights, pad' = R-1-pad.
         # A flip pass + KC (ds_read_b128) B operand measures faster than reading the
