@@ -412,6 +412,22 @@ def _grouped_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
     return torch.empty(n, dtype=torch.float32, device=device), n
 
 
+PATCH_DGRAD = "conv_patch_dgrad"
+PATCH_MIN_ROWS, PATCH_MAX_COLS = 8, 32  # a 256-pixel band of at most 32 columns has at least 8 rows
+
+
+def patch_dgrad_ok(s: ConvSpec) -> bool:
+    """Data gradients the patch-resident kernel takes (csrc/kernels/conv_patch.hip): 5x5 window,
+    stride 1, pad 2, no dilation, 128 output and 48 input channels per group (CaffeNet conv2).
+    A block stages a band of whole rows plus 4 halo rows, so the image must be at least
+    PATCH_MIN_ROWS high and wide for the halo to pay and at most PATCH_MAX_COLS wide for a band
+    to hold that many rows; smaller and wider images keep the implicit GEMM.  The switch is read
+    on every call (SN_FEATURES=conv_patch=0)."""
+    return (s.R == 5 and s.S == 5 and _unit_conv(s) and s.ph == 2 and s.pw == 2 and s.Kg == 128 and s.Cg == 48
+            and PATCH_MIN_ROWS <= s.H and PATCH_MIN_ROWS <= s.W <= PATCH_MAX_COLS
+            and s.N * s.H * s.W < _GROUPED_MAX_PIX and features.enabled("conv_patch"))
+
+
 def _side_covers(t: torch.Tensor) -> bool:
     from . import gemm as G
     return G._SIDE is not None and G._SIDE.covers(t)  # a fused fp8 side output needs the GEMM epilogue
@@ -746,6 +762,11 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out):
                 and not DGRAD_INPLACE_WEIGHTS and not _side_covers(dx)):
             call("conv3x3_direct", dy, _flipped(w, s, ws.wt), None, _c(gate) if gate is not None else None, dx,
                  s.N, s.H, s.W, 64, 64, 1, 0, 0)
+            return dx
+        if (patch_dgrad_ok(s) and ldd == s.K and ldo == s.C and not DGRAD_INPLACE_WEIGHTS
+                and _dw_io_ok(dy, dx, gate) and not _side_covers(dx)):
+            # dy staged in LDS once per band instead of once per tap; the GEMM's summation order
+            call(PATCH_DGRAD, dy, _flipped(w, s, ws.wt), gate, dx, s.N, s.H, s.W, s.groups, ldd, ldo, 1.0, 0)
             return dx
         A = Im2col(dy, g2, kcontig=True, gstride=s.Kg)
         if DGRAD_INPLACE_WEIGHTS:
