@@ -23,6 +23,7 @@
 // variance formula (Chan et al.), never E[x^2] - E[x]^2; the count of a partial follows from
 // the geometry and is not stored.
 #include "common.h"
+#include "row_io.h"  // ldx / stx
 
 namespace {
 
@@ -55,33 +56,6 @@ inline Plan make_plan(long long R, long long C, int V) {
   p.rps = (R + want - 1) / want;
   p.slabs = (int)((R + p.rps - 1) / p.rps);
   return p;
-}
-
-template <int V, int DT>
-SN_DEV void ldx(const void* p, long long e, float* f) {
-  if constexpr (V == 8) {
-    unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(p) + e), f);
-  } else if constexpr (V == 4) {
-    const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + e);
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
-  } else if constexpr (DT) {
-    f[0] = reinterpret_cast<const float*>(p)[e];
-  } else {
-    f[0] = bf2f(reinterpret_cast<const bf16_t*>(p)[e]);
-  }
-}
-
-template <int V, int DT>
-SN_DEV void stx(void* p, long long e, const float* f) {
-  if constexpr (V == 8) {
-    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p) + e) = pack8(f);
-  } else if constexpr (V == 4) {
-    *reinterpret_cast<float4*>(reinterpret_cast<float*>(p) + e) = make_float4(f[0], f[1], f[2], f[3]);
-  } else if constexpr (DT) {
-    reinterpret_cast<float*>(p)[e] = f[0];
-  } else {
-    reinterpret_cast<bf16_t*>(p)[e] = f2bf(f[0]);
-  }
 }
 
 // mean and inv_std of channels c0 .. c0 + V - 1.  ST_BATCH: sa = mean, sb = inv_std.

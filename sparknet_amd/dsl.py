@@ -225,6 +225,15 @@ def EltwiseLayer(name, bottom, operation="SUM", *, coeff=None, top=None, stable_
     return lp
 
 
+def AxpyLayer(name, bottom, *, top=None):
+    """``top = a * x + y`` from bottoms ``[a, x, y]``: the tail of a squeeze-and-excitation block."""
+    return _base("Axpy", name, bottom, top)
+
+
+def SigmoidLayer(name, bottom, *, top=None, in_place=False):
+    return _base("Sigmoid", name, bottom, list(bottom) if in_place else top)
+
+
 def NetParam(name, *layers):
     net = proto.NetParameter(name=name)
     for lp in layers:
@@ -284,4 +293,6 @@ batch_norm_layer = BatchNormLayer
 scale_layer = ScaleLayer
 bias_layer = BiasLayer
 eltwise_layer = EltwiseLayer
+axpy_layer = AxpyLayer
+sigmoid_layer = SigmoidLayer
 net_param = NetParam

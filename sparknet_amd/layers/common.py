@@ -21,6 +21,7 @@ import torch
 
 from .. import ops
 from ..core.layer import Layer, register
+from ..utils import features
 
 
 def _phys_axis(blob, axis):
@@ -57,6 +58,12 @@ def _to_logical(blob, diff=False):
 def _as(t, dtype):
     """``t`` in ``dtype`` (a 2-D Input blob is fp32 next to bf16 activations): a HIP cast if needed."""
     return t if t.dtype == dtype else _lh().cast(t, dtype)
+
+
+def _nc_coef(blob):
+    """fp32 [N][C] coefficient from an (N, C) or (N, C, 1, 1) GPU blob: both are stored as N
+    contiguous C-vectors, so the bytes are read in place (a HIP cast if the blob is bf16)."""
+    return _as(blob.data, torch.float32)
 
 
 def _from_logical(t, blob):
@@ -1000,11 +1007,15 @@ class _BroadcastLayer(Layer):
     Layout.  4-D blobs are stored NHWC, so the covered axes form one ``[outer][A][inner]``
     decomposition of the storage only when they are adjacent there (C, H, W, HW, N, CHW, NCHW,
     scalar); a multi-axis param is then kept in storage order and ``to_caffe`` / ``from_caffe``
-    permute, as for the conv weights.  The other combinations — (N,C), (N,C,H), (C,H) — run on
-    an NCHW copy.  Non-4-D blobs are stored plain and always decompose.
+    permute, as for the conv weights.  (N,C) — the squeeze-and-excitation gate — is not adjacent
+    but is the natural shape of the storage all the same: image n's coefficient is one contiguous
+    C-vector, in Caffe's order (``nc``).  The other combinations — (N,C,H), (C,H) — run on an
+    NCHW copy, and so does (N,C) with ``SN_FEATURES=se_kernels=0``.  Non-4-D blobs are stored
+    plain and always decompose.
 
     GPU: ``inner == 1`` (per-channel, whole-shape, scalar) runs the vectorised per-channel
-    kernels of csrc/kernels/bn_scale.hip without normalisation; ``inner > 1`` a plain
+    kernels of csrc/kernels/bn_scale.hip without normalisation; ``nc`` the per-image kernels of
+    csrc/kernels/se.hip on the NHWC tensors (one launch each way); ``inner > 1`` a plain
     broadcast kernel plus ``axis_reduce``."""
     min_bottoms = 1
     max_bottoms = 2
@@ -1040,6 +1051,10 @@ class _BroadcastLayer(Layer):
         b0 = bottoms[0]
         a, k = self.axis, self.k
         S = b0.shape
+        # (N, C) on an image blob: the coefficient of image n is one contiguous C-vector of the
+        # NHWC storage, in Caffe's order — the GPU runs csrc/kernels/se.hip on the blobs as they
+        # are stored (the fields below still describe the NCHW-copy route: CPU path, switch off)
+        self.nc = b0.is_image and (a, k) == (0, 2) and features.enabled("se_kernels")
         self.cshape = tuple(S[a:a + k])
         self.logical = (b0.count_range(0, a), b0.count_range(a, a + k), b0.count_range(a + k))
         self.perm = list(range(k))
@@ -1183,7 +1198,53 @@ class _BroadcastLayer(Layer):
             return lh.bn_fwd(x, o, A, lh.NO_STATS, s, b, False)
         return lh.axis_scale_bias(x, s, b, A, i)
 
+    def _forward_nc(self, bottoms, tops):
+        """(N, C) route: one nc_affine_fwd on the NHWC tensor, no layout copies."""
+        b0 = bottoms[0]
+        two = len(bottoms) == 2
+        N, C_, H, W = b0.shape
+        x = _as(b0.data, tops[0].dtype)
+        s = b = None
+        if self.has_scale:
+            s = _nc_coef(bottoms[1]) if two else self.scale.data
+            self._x, self._s = x, s
+        if self.bias is not None:
+            b = self.bias.data
+        elif not self.has_scale:
+            b = _nc_coef(bottoms[1])
+        tops[0].data = _lh().nc_affine_fwd(x, N, H * W, C_, s, b)
+
+    def _backward_nc(self, tops, propagate_down, bottoms):
+        """One nc_affine_bwd: dx, the (N, C) scale gradient and the (N, C) bias gradient together."""
+        lh = _lh()
+        two = len(bottoms) == 2
+        N, C_, H, W = bottoms[0].shape
+        dy = _as(tops[0].diff, tops[0].data.dtype)
+        ds = db = None
+        sflag = bflag = lh.GRAD_SKIP
+        fresh = lambda: torch.empty(N * C_, dtype=torch.float32, device=dy.device)
+        if self.bias is not None:
+            bi = self.params.index(self.bias)
+            if self.param_grads_needed(bi):
+                db, bflag = self.bias.diff, self._flag(bi)
+        if self.has_scale:
+            if two and propagate_down[1]:
+                ds, sflag = fresh(), lh.GRAD_STORE
+            elif not two and self.param_grads_needed(0):
+                ds, sflag = self.scale.diff, self._flag(0)
+        elif two and propagate_down[1]:
+            db, bflag = fresh(), lh.GRAD_STORE
+        want_dx = bool(propagate_down[0]) and self.has_scale
+        dx = lh.nc_affine_bwd(dy, N, H * W, C_, s=self._s if want_dx else None, x=self._x if sflag else None,
+                              want_dx=want_dx, ds=ds, sflag=sflag, db=db, bflag=bflag)
+        if two and propagate_down[1]:
+            self._grad_to_bottom1(ds if self.has_scale else db, bottoms[1])
+        if propagate_down[0]:
+            bottoms[0].diff = _as(dx if want_dx else tops[0].diff, bottoms[0].dtype)
+
     def _forward_gpu(self, bottoms, tops):
+        if self.nc:
+            return self._forward_nc(bottoms, tops)
         b0 = bottoms[0]
         two = len(bottoms) == 2
         x = _as(b0.data if self.phys is not None else _to_logical(b0), tops[0].dtype)
@@ -1221,6 +1282,8 @@ class _BroadcastLayer(Layer):
         return lh.GRAD_STORE if self.grad_overwrite(i) else lh.GRAD_ACC
 
     def _backward_gpu(self, tops, propagate_down, bottoms):
+        if self.nc:
+            return self._backward_nc(tops, propagate_down, bottoms)
         two = len(bottoms) == 2
         dy = _as(tops[0].diff if self.phys is not None else _to_logical(tops[0], diff=True), tops[0].data.dtype)
         if self.bias is not None:
@@ -1273,6 +1336,97 @@ class BiasLayer(_BroadcastLayer):
         self.scale = self.bias = None
         if len(bottoms) == 1:
             self.bias = self._add_coef(p.filler if p.HasField("filler") else None, 0.0)
+
+
+@register("Axpy")
+class AxpyLayer(Layer):
+    """The tail of a squeeze-and-excitation block (axpy_layer of the SENet release, Hu et al.
+    2018): ``top = a * x + y`` with bottoms ``[a, x, y]`` — a per-image, per-channel gate
+    (N, C) or (N, C, 1, 1), the block output (N, C, H, W) and the shortcut.  Backward:
+    ``da = sum_hw dtop * x``, ``dx = a * dtop``, ``dy = dtop``.  No parameters.
+
+    GPU: one nc_affine_fwd and one nc_affine_bwd (csrc/kernels/se.hip) on the NHWC tensors.
+    With ``SN_FEATURES=se_kernels=0`` the same result is composed from the routes a
+    ``Scale (axis 0)`` + ``Eltwise SUM`` pair takes without those kernels: the scale on an
+    NCHW copy, then eltwise_fwd / eltwise_bwd (the product stays fp32 between the two forward
+    launches: one rounding of the sum on either route)."""
+    exact_bottoms = 3
+    exact_tops = 1
+
+    def reshape(self, bottoms, tops):
+        a, x, y = bottoms
+        if len(x.shape) != 4 or x.shape != y.shape:
+            raise ValueError(f"Axpy {self.name!r}: x {x.shape} and y {y.shape} must be equal 4-D shapes")
+        if tuple(a.shape) not in (x.shape[:2], x.shape[:2] + (1, 1)):
+            raise ValueError(f"Axpy {self.name!r}: a {a.shape} must be (N, C) or (N, C, 1, 1) of x {x.shape}")
+        tops[0].reshape(x.shape, x.dtype)
+
+    def forward(self, bottoms, tops):
+        a, x, y = bottoms
+        N, C_, H, W = x.shape
+        if x.data.is_cuda:
+            return self._forward_gpu(bottoms, tops)
+        s = a.nchw().float().reshape(N, C_, 1, 1)
+        self._x, self._s = x.nchw().float(), s
+        _BroadcastLayer._to_blob(s * self._x + y.nchw().float(), tops[0])
+
+    def backward(self, tops, propagate_down, bottoms):
+        a, x, y = bottoms
+        if tops[0].diff.is_cuda:
+            return self._backward_gpu(tops, propagate_down, bottoms)
+        dt = tops[0].nchw(diff=True).float()
+        if propagate_down[0]:
+            g = (dt * self._x).sum(dim=(2, 3))
+            a.diff = (g.reshape(a.shape).permute(0, 2, 3, 1) if a.is_image else g).contiguous().to(a.dtype)
+        if propagate_down[1]:
+            x.diff = (dt * self._s).permute(0, 2, 3, 1).contiguous().to(x.dtype)
+        if propagate_down[2]:
+            y.diff = dt.permute(0, 2, 3, 1).contiguous().to(y.dtype)
+
+    # -- GPU path (HIP only) -------------------------------------------------------------
+    def _forward_gpu(self, bottoms, tops):
+        lh = _lh()
+        a, x, y = bottoms
+        N, C_, H, W = x.shape
+        dtype = tops[0].dtype
+        s = _nc_coef(a)
+        xd, yd = _as(x.data, dtype), _as(y.data, dtype)
+        self._x, self._y, self._s = xd, yd, s
+        self._se = features.enabled("se_kernels")
+        if self._se:
+            tops[0].data = lh.nc_affine_fwd(xd, N, H * W, C_, s=s, r=yd)
+            return
+        # the product stays fp32 between the two launches, so that the sum is rounded once, as in the kernel
+        f32 = torch.float32
+        scaled = lh.axis_scale_bias(lh.nhwc_to_nchw(xd, f32), s.reshape(-1), None, N * C_, H * W)
+        t, _ = lh.eltwise_fwd(1, [lh.nchw_to_nhwc(scaled.reshape(N, C_, H * W), N, C_, H, W), _as(yd, f32)], [1.0, 1.0])
+        tops[0].data = _as(t, dtype)
+
+    def _backward_gpu(self, tops, propagate_down, bottoms):
+        lh = _lh()
+        a, x, y = bottoms
+        N, C_, H, W = x.shape
+        dt = _as(tops[0].diff, tops[0].data.dtype)
+        pa, px, py = (bool(p) for p in propagate_down[:3])
+        da = dx = None
+        if self._se:
+            if pa or px:
+                da = torch.empty(N * C_, dtype=torch.float32, device=dt.device) if pa else None
+                dx = lh.nc_affine_bwd(dt, N, H * W, C_, s=self._s if px else None, x=self._x if pa else None,
+                                      want_dx=px, ds=da, sflag=lh.GRAD_STORE if pa else lh.GRAD_SKIP)
+        elif pa or px:
+            g = lh.nhwc_to_nchw(lh.eltwise_bwd(1, [self._x, self._y], [1.0, 1.0], 0, False, tops[0].data, dt, None))
+            if pa:
+                da = lh.axis_reduce(lh.RED_DOT, g, lh.nhwc_to_nchw(self._x), 1, 1, N * C_, H * W)
+            if px:
+                gx = lh.axis_scale_bias(g, self._s.reshape(-1), None, N * C_, H * W)
+                dx = lh.nchw_to_nhwc(gx.reshape(N, C_, H * W), N, C_, H, W)
+        if pa:
+            a.diff = _as(da, a.dtype).reshape(a.data.shape)
+        if px:
+            x.diff = _as(dx, x.dtype)
+        if py:  # the shortcut's gradient is dtop: handed over as Eltwise SUM with coefficient 1 does
+            y.diff = _as(lh.eltwise_bwd(1, [self._x, self._y], [1.0, 1.0], 1, False, tops[0].data, dt, None), y.dtype)
 
 
 @register("SPP")

@@ -14,6 +14,8 @@
   pointwise 1x1 blocks, each conv followed by BatchNorm -> Scale -> ReLU)
 * ``resnext50``      — not in the reference; ResNeXt-50 32x4d (Xie et al. 2017): ResNet-50's stem and
   head around bottlenecks whose 3x3 is a 32-group convolution carrying the stage's stride
+* ``se_resnet50``    — not in the reference; SE-ResNet-50 (Hu et al. 2018): ResNet-50 with a squeeze-and-
+  excitation tail per block (global pool, two 1x1 convolutions, Sigmoid) gating the block output in an Axpy
 
 Each builder returns a NetParameter whose data entry points are SparkNet ``JavaData``
 layers (TRAIN and TEST variants, like ProtoLoader.replaceDataLayers), and each has a
@@ -22,9 +24,9 @@ matching ``*_solver`` with the reference hyper-parameters.
 from __future__ import annotations
 
 from .. import proto
-from ..dsl import (AccuracyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer, Include,
-                   InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer, ScaleLayer,
-                   SoftmaxWithLoss)
+from ..dsl import (AccuracyLayer, AxpyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer,
+                   Include, InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer,
+                   ScaleLayer, SigmoidLayer, SoftmaxWithLoss)
 
 WB = [(1.0, 1.0), (2.0, 0.0)]   # weight / bias lr & decay mults used by the ImageNet models
 W12 = [{"lr_mult": 1.0}, {"lr_mult": 2.0}]
@@ -383,6 +385,56 @@ def resnext50(train_batch=32, test_batch=50, crop=224, classes=1000):
     return resnext(train_batch=train_batch, test_batch=test_batch, crop=crop, classes=classes)
 
 
+def _se_block(L, tag, bottom, width, stride, project, reduction):
+    """res{tag}: ResNet-50's bottleneck with a squeeze-and-excitation tail after scale{tag}_branch2c —
+    global average pool, 1x1 down (ReLU), 1x1 up, Sigmoid — whose gate scales the block output
+    inside the shortcut sum (Axpy: csrc/kernels/se.hip)."""
+    short = bottom
+    if project:
+        short = _conv_bn(L, f"res{tag}_branch1", f"{tag}_branch1", bottom, 1, 4 * width, stride=stride, relu=False)
+    x = _conv_bn(L, f"res{tag}_branch2a", f"{tag}_branch2a", bottom, 1, width, stride=stride)
+    x = _conv_bn(L, f"res{tag}_branch2b", f"{tag}_branch2b", x, 3, width, pad=1)
+    x = _conv_bn(L, f"res{tag}_branch2c", f"{tag}_branch2c", x, 1, 4 * width, relu=False)
+    se = f"res{tag}_se"
+    L += [PoolingLayer(se + "_pool", [x], Pooling.Ave, global_pooling=True),
+          _conv(se + "_down", se + "_pool", 1, 4 * width // reduction, wf=MSRA, bf=_c(0.0)),
+          _relu(se + "_down_relu", se + "_down"),
+          _conv(se + "_up", se + "_down", 1, 4 * width, wf=MSRA, bf=_c(0.0)),
+          SigmoidLayer(se + "_gate", [se + "_up"]),
+          AxpyLayer(f"res{tag}", [se + "_gate", x, short]), _relu(f"res{tag}_relu", f"res{tag}")]
+    return f"res{tag}"
+
+
+def se_resnet(reps=(3, 4, 6, 3), reduction=16, train_batch=32, test_batch=50, crop=224, classes=1000):
+    """SE-ResNet (Hu et al. 2018, "Squeeze-and-Excitation Networks"): not in the reference.
+    ResNet-50's stem, bottlenecks and layer names with a squeeze-and-excitation tail per block:
+    ``res{tag}_se_pool`` (global average), ``_se_down`` (1x1 convolution with bias to
+    4 width / ``reduction``) with the in-place ``_se_down_relu``, ``_se_up`` (1x1 back to 4 width),
+    ``_se_gate`` (Sigmoid), and ``res{tag}`` as an ``Axpy [gate, res{tag}_branch2c, shortcut]`` in
+    place of the Eltwise SUM.  The block structure follows the public SENet Caffe release (the two
+    SE products as 1x1 convolutions with bias, the Axpy tail); the names of the SE layers are this
+    project's own — the release's prototxt was not at hand to compare, so a public .caffemodel
+    will need its SE layers renamed.  At the defaults (SE-ResNet-50) 28 088 024 learnable elements
+    besides the BatchNorm statistics: ResNet-50's 25 557 032 plus 2 530 992 in the sixteen SE pairs."""
+    L = list(data_layers(train_batch, test_batch, 3, crop, crop))
+    x = _conv_bn(L, "conv1", "_conv1", "data", 7, 64, stride=2, pad=3)
+    L.append(_pool("pool1", x, 3, 2))
+    x = "pool1"
+    for stage, n in enumerate(reps, 2):
+        width = 64 * 2 ** (stage - 2)
+        for r in range(n):
+            x = _se_block(L, f"{stage}{chr(ord('a') + r)}", x, width, 2 if (r == 0 and stage > 2) else 1, r == 0,
+                          reduction)
+    L += [PoolingLayer("pool5", [x], Pooling.Ave, global_pooling=True),
+          _ip(f"fc{classes}", "pool5", classes, MSRA, _c(0.0)), *_head(f"fc{classes}", top5=True)]
+    return NetParam("SE-ResNet", *L)
+
+
+def se_resnet50(train_batch=32, test_batch=50, crop=224, classes=1000):
+    """SE-ResNet-50: :func:`se_resnet` at its defaults."""
+    return se_resnet(train_batch=train_batch, test_batch=test_batch, crop=crop, classes=classes)
+
+
 # --- solvers ------------------------------------------------------------------------------
 
 def _solver(net, **kw):
@@ -451,13 +503,18 @@ def resnext50_solver(net=None):  # ResNet-50's schedule
                    gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
 
 
+def se_resnet50_solver(net=None):  # ResNet-50's schedule
+    return _solver(net or se_resnet50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
+                   gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
+
+
 MODELS = {
     "lenet": (lenet, lenet_solver), "cifar10_quick": (cifar10_quick, cifar10_quick_solver),
     "cifar10_full": (cifar10_full, cifar10_full_solver), "caffenet": (caffenet, caffenet_solver),
     "alexnet": (alexnet, alexnet_solver), "googlenet": (googlenet, googlenet_solver),
     "vgg16": (vgg16, vgg16_solver), "resnet50": (resnet50, resnet50_solver),
     "resnet_cifar": (resnet_cifar, resnet_cifar_solver), "mobilenet": (mobilenet, mobilenet_solver),
-    "resnext50": (resnext50, resnext50_solver),
+    "resnext50": (resnext50, resnext50_solver), "se_resnet50": (se_resnet50, se_resnet50_solver),
 }
 
 

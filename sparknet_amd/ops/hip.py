@@ -19,7 +19,7 @@ from . import _lib
 from ..utils import features
 from .gemm import (EPI_BF16, EPI_F32, EPI_F32_ACC, ConvGeom, Dense, FlipW, Fp8Side, Im2col, colsum, fp8_side_output,
                    gemm, linear_dgrad, linear_fwd, linear_wgrad, side_bytes)
-from .spec import POOL_MAX, ConvNdSpec, ConvSpec, PoolSpec
+from .spec import POOL_AVE, POOL_MAX, ConvNdSpec, ConvSpec, PoolSpec
 
 call = _lib.call
 BF16 = torch.bfloat16
@@ -989,11 +989,23 @@ def _side_args(side, t, n0, n1):
     return (side.q[n0:n1], side.slot, side.part, int(side.e5m2))
 
 
+def gap_ok(s: PoolSpec, x, side=None) -> bool:
+    """A global average pooling that runs on sn_gap_fwd (csrc/kernels/se.hip): the window is the
+    whole unpadded image, bf16, no fp8 side output.  Windows of 64 positions or fewer (the 7x7 and
+    8x8 heads of the classification nets) stay on avepool_fwd, so that their bits do not change."""
+    return (s.method == POOL_AVE and s.kh == s.H and s.kw == s.W and s.ph == 0 and s.pw == 0
+            and s.P == 1 and s.Q == 1 and side is None and x.dtype == BF16 and s.H * s.W > 64
+            and features.enabled("se_kernels"))
+
+
 def pool_forward_mask(x, s: PoolSpec, gate: bool = False, side=None):
     """gate=True (MAX only): x is the output of a slope-0 in-place ReLU whose backward is
     folded into the argmax mask (windows with max <= 0 pass no gradient).  side: an
     ops.gemm.Fp8Side over the output (pool_side_ok): the kernel also stores its fp8 bytes."""
     x = _c(x)
+    if gap_ok(s, x, side):
+        from . import layers_hip
+        return layers_hip.gap_fwd(x, s.N, s.H * s.W, s.C), None
     if side is not None:
         assert pool_side_ok(s, False) and tuple(side.base.shape) == (s.N, s.P, s.Q, s.C)
         y = side.base

@@ -1,7 +1,8 @@
 """ctypes wrappers of ``csrc/kernels/layers.hip``: the non-hot Caffe layer families on the
 GPU (neurons, PReLU, Eltwise, BatchNorm / MVN, axis copies, layout changes, row gathers /
 scatter-adds, Reduction, ArgMax, Caffe-ordered Im2col, the loss family) and of
-``csrc/kernels/bn_scale.hip`` (fused BatchNorm -> Scale -> ReLU, per-channel Scale / Bias).
+``csrc/kernels/bn_scale.hip`` (fused BatchNorm -> Scale -> ReLU, per-channel Scale / Bias) and
+``csrc/kernels/se.hip`` (global average pool, per-image per-channel affine: Axpy, (N, C) Scale / Bias).
 
 Every function launches HIP kernels on torch's current stream (graph-capturable); torch is
 used only to allocate outputs.  Tensors must be contiguous bf16 or fp32 device tensors.
@@ -210,6 +211,62 @@ def axis_scale_bias(x, s, b, A, inner):
 def cast(x, dtype):
     """Copy of x in another supported dtype."""
     return neuron_fwd("Power", x, dtype, 1.0, 1.0, 0.0)
+
+
+# -- squeeze-and-excitation: global average pool, per-(image, channel) affine (csrc/kernels/se.hip) ----
+# x / r / y / dy / dx: contiguous [N][HW][C_] tensors of one dtype (bf16 or fp32); the coefficients
+# s / b and the gradients ds / db are fp32 [N][C_] (any shape of N * C_ elements).
+def _nc_part(t, N, HW, C_):
+    k = _lib.kernels()
+    k.sn_nc_part_floats.restype = C.c_longlong
+    n = int(k.sn_nc_part_floats(C.c_longlong(N), C.c_longlong(HW), C.c_longlong(C_), C.c_longlong(dt(t))))
+    if n < 0:
+        raise ValueError(f"layers_hip: unsupported per-image geometry N={N} HW={HW} C={C_}")
+    return (torch.empty(n, dtype=torch.float32, device=t.device) if n else None), n
+
+
+def _nc_vec(v, N, C_, out=False):
+    if v is None:
+        return None
+    if v.dtype != torch.float32 or v.numel() != N * C_ or (out and not v.is_contiguous()):
+        raise ValueError(f"layers_hip: an (N, C) coefficient must be {'contiguous ' if out else ''}fp32 with "
+                         f"{N * C_} elements, got {v.dtype} {tuple(v.shape)}")
+    return _c(v)
+
+
+def gap_fwd(x, N, HW, C_):
+    """y[n, c] = mean over the HW rows of image n, accumulated in fp32: (N, 1, 1, C_) in x's dtype."""
+    x = _c(x)
+    part, n = _nc_part(x, N, HW, C_)
+    y = torch.empty((N, 1, 1, C_), dtype=x.dtype, device=x.device)
+    call("gap_fwd", x, y, dt(x), N, HW, C_, part, n)
+    return y
+
+
+def nc_affine_fwd(x, N, HW, C_, s=None, b=None, r=None):
+    """y = x * s[n, c] + b[n, c] + r in one pass (each of s, b, r may be None)."""
+    x = _c(x)
+    if r is not None and (r.dtype != x.dtype or r.numel() != x.numel()):
+        raise ValueError("layers_hip: nc_affine_fwd's r must match x in dtype and size")
+    y = torch.empty_like(x)
+    call("nc_affine_fwd", x, _c(r), y, dt(x), N, HW, C_, _nc_vec(s, N, C_), _nc_vec(b, N, C_))
+    return y
+
+
+def nc_affine_bwd(dy, N, HW, C_, s=None, x=None, want_dx=True, ds=None, sflag=GRAD_SKIP, db=None, bflag=GRAD_SKIP):
+    """One pass over dy (and x when ``sflag``): returns dx = dy * s (None unless ``want_dx``);
+    ds (+)= sum over HW of dy * x and db (+)= sum over HW of dy under the GRAD_* flags."""
+    dy = _c(dy)
+    if sflag != GRAD_SKIP and (x is None or x.dtype != dy.dtype or x.numel() != dy.numel()):
+        raise ValueError("layers_hip: nc_affine_bwd's ds needs x in dy's dtype and size")
+    if want_dx and s is None:
+        raise ValueError("layers_hip: nc_affine_bwd's dx needs s (without a scale dx is dy itself)")
+    part, n = _nc_part(dy, N, HW, C_) if (sflag != GRAD_SKIP or bflag != GRAD_SKIP) else (None, 0)
+    dx = torch.empty_like(dy) if want_dx else None
+    call("nc_affine_bwd", dy, _c(x) if sflag != GRAD_SKIP else None, dx, dt(dy), N, HW, C_, _nc_vec(s, N, C_), part, n,
+         _nc_vec(ds, N, C_, True) if sflag != GRAD_SKIP else None, sflag,
+         _nc_vec(db, N, C_, True) if bflag != GRAD_SKIP else None, bflag)
+    return dx
 
 
 # -- eltwise -------------------------------------------------------------------------------

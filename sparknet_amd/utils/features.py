@@ -39,6 +39,8 @@ DEFAULTS = {
     "conv_depthwise": True,     # per-channel kernels for depthwise 3x3 convs (0: one im2col + GEMM per group)
     "conv_grouped": True,       # 16-channel bundle kernels for narrow-group 3x3 convs, Cg == Kg in {4, 8, 16} (0: implicit grouped GEMM / per-group loop)
     "conv_patch": True,         # patch-resident data gradient of 5x5 grouped convs, 128 -> 48 channels per group (CaffeNet conv2; 0: implicit grouped GEMM)
+    # per-image, per-channel kernels (csrc/kernels/se.hip)
+    "se_kernels": True,         # global average pool over > 64 positions, Scale / Bias with an (N, C) coefficient and Axpy on the NHWC storage (0: avepool_fwd, the NCHW-copy route plus Eltwise)
     # fp8 details
     "fp8_wgrad_bias": True,     # fp8 weight-gradient bias through the e4m3 ones column
     "fp8_side_frag": True,      # per-fragment epilogues also store the fp8 side output
