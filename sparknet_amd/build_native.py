@@ -42,6 +42,11 @@ HIP_FLAGS = [
     "-munsafe-fp-atomics",
     f"-I{CSRC / 'kernels'}",
 ]
+# Extra hipcc flags of single kernel files.  conv_tstride.hip opts out of the compiler's packed
+# fp32 VALU forms (v_pk_{add,mul,fma}_f32) as a precaution: the compiler emits none for it today
+# with or without the flag, no result was seen to differ, and the flag keeps a later edit of its
+# epilogue from bringing them in unnoticed.  The older files are built as they always were.
+HIP_TU_FLAGS = {"conv_tstride.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # host C++ runtime: g++ against the HIP runtime API (hipHostMalloc / hipMemcpyAsync /
 # events); the HIP platform macro selects the AMD backend of the runtime headers.
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall", f"-I{CSRC / 'runtime'}",
@@ -113,7 +118,7 @@ def _compile(src: Path, hip: bool, extra: list[str] | None = None) -> Path:
     if _stale(obj, _deps(src)) or (hip and (not rep.exists() or rep.stat().st_mtime < obj.stat().st_mtime)):
         obj.parent.mkdir(parents=True, exist_ok=True)
         if hip:
-            cmd = [HIPCC, *HIP_FLAGS, "-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o", str(obj)]
+            cmd = [HIPCC, *HIP_FLAGS, *HIP_TU_FLAGS.get(src.name, []), "-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o", str(obj)]
         else:
             cmd = ["g++", *CXX_FLAGS, *(extra or []), "-c", str(src), "-o", str(obj)]
         r = _run(cmd)

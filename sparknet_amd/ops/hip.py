@@ -428,6 +428,25 @@ def patch_dgrad_ok(s: ConvSpec) -> bool:
             and s.N * s.H * s.W < _GROUPED_MAX_PIX and features.enabled("conv_patch"))
 
 
+TSTRIDE_DGRAD = "conv_tstride_dgrad"
+TSTRIDE_MIN_PIX = 64  # output-gradient pixels (N P Q) below which the generic route stays
+
+
+def tstride_ok(s: ConvSpec) -> bool:
+    """Data gradients the phase-decomposed kernel takes (csrc/kernels/conv_tstride.hip): ungrouped,
+    stride 2 on both axes, no dilation, a window of at most 4 x 4, any pad, whole 8-channel lanes
+    on both sides, every image below 2^31 elements (sn_conv_tstride_dgrad's geometry check).  The
+    lower bound of TSTRIDE_MIN_PIX output-gradient pixels is not a measured speed threshold: a
+    block covers 8 x 16 cells, so a launch below it is mostly tile padding, and it keeps the
+    smallest strided shapes (the 2 x 8 x 8 ones the launch-trace fixture pins) on the generic
+    route.  Larger windows, other strides, groups, dilation, fp8 and the fp32-device mode keep
+    their routes.  The switch is read on every call (SN_FEATURES=conv_tstride=0)."""
+    return (s.groups == 1 and s.sh == 2 and s.sw == 2 and s.dh == 1 and s.dw == 1 and 1 <= s.R <= 4 and 1 <= s.S <= 4
+            and s.K % 8 == 0 and s.C % 8 == 0 and s.P > 0 and s.Q > 0 and s.N * s.P * s.Q >= TSTRIDE_MIN_PIX
+            and s.H * s.W * s.C < 2 ** 31 and (s.P + 4) * (s.Q + 4) * s.K < 2 ** 31 and max(s.ph, s.pw) <= 1 << 20
+            and features.enabled("conv_tstride"))
+
+
 def _side_covers(t: torch.Tensor) -> bool:
     from . import gemm as G
     return G._SIDE is not None and G._SIDE.covers(t)  # a fused fp8 side output needs the GEMM epilogue
@@ -777,6 +796,11 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out):
         return dx
     if ldd == s.K and depthwise_ok(s) and _dw_io_ok(dy, w, dx, gate) and not _side_covers(dx):
         call("conv_dw_dgrad", dy, w, gate, dx, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
+        return dx
+    if (ldd == s.K and ldo == s.C and tstride_ok(s) and ws.fp8_dgrad is None and _dw_io_ok(dy, w, dx, gate)
+            and not _side_covers(dx)):
+        # all four output phases of a stride-2 window from one staged dy patch: no dcol, no col2im
+        call(TSTRIDE_DGRAD, dy, w, gate, dx, s.N, s.H, s.W, s.C, s.K, s.R, s.S, s.ph, s.pw)
         return dx
     # generic: dcol = dy_g @ W_g, then col2im (gather, no atomics)
     assert ldd == s.K
