@@ -9,8 +9,9 @@ TB/s is the effective rate of the bytes each product must move (one input-sized 
 output-sized activation; weights and slab partials are not counted), next to a device copy of the
 same number of bytes.  Every tensor here is below the 256 MiB Infinity Cache and the launches repeat
 on the same buffers, so the copy runs above the HBM stream rate and the kernels may be served from
-the cache as well: the TB/s column compares the two, it is not an HBM rate.  Cg = 32 (stage 5) has
-no instance: its rows show the parent path only.
+the cache as well: the TB/s column compares the two, it is not an HBM rate.  Cg = 32 (stage 5) is
+not conv_grouped.hip's: its rows show whatever route it takes (scripts/wgroup_probe.py compares
+csrc/kernels/conv_wgroup.hip with its parent route).
 
     python scripts/grouped_probe.py [--batch 64]
 """

@@ -257,6 +257,9 @@ def conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=Non
     if direct_io and ldy == s.K and grouped_ok(s) and _dw_io_ok(x, w, y):
         call(GROUPED_FWD, x, w, b, y, s.N, s.H, s.W, s.C, s.Cg, s.sh, s.sw, s.ph, s.pw, int(relu))
         return y
+    if direct_io and ldy == s.K and wgroup_ok(s) and _dw_io_ok(x, w, y):
+        call(WGROUP_FWD, x, w, b, y, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw, int(relu))
+        return y
     if _implicit_ok(s):
         kred = s.R * s.S * s.Cg
         A = Im2col(x, _geom(s, ldx), kcontig=True, gstride=s.Cg)
@@ -409,6 +412,35 @@ def _grouped_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
     n = int(k.sn_conv_grouped_part_floats(*(C.c_longlong(v) for v in (s.N, s.P, s.Q, s.C, s.Cg))))
     if n <= 0:
         raise ValueError(f"grouped weight gradient: unsupported geometry {s}")
+    return torch.empty(n, dtype=torch.float32, device=device), n
+
+
+WGROUP_FWD, WGROUP_WGRAD, WGROUP_DGRAD = "conv_wgroup_fwd", "conv_wgroup_wgrad", "conv_wgroup_dgrad"
+_WGROUP_PINNED_DENSE = (8, 8)  # image size of the ungrouped 32 -> 32 layers the launch-trace fixture pins
+
+
+def wgroup_ok(s: ConvSpec) -> bool:
+    """32-wide grouped 3x3 convolutions the dense per-group kernels take (csrc/kernels/conv_wgroup.hip:
+    ResNeXt's last stage): Cg == Kg == 32, whole groups, strides 1 or 2 per axis, no dilation, the
+    pixel and pad limits of grouped_ok (sn_conv_wgroup_*'s geometry check).  Cg = 64, Cg != Kg and
+    other windows keep the implicit grouped GEMM.  An ungrouped 32 -> 32 layer is one 32-wide group
+    and is taken like any other, with one exception that is not a measured threshold: ungrouped
+    8 x 8 images stay on the implicit GEMM, because tests/conv_launch_trace.json pins that shape's
+    fp8, side-output, chunked and channel-slice launches there.  The switch is read on every call
+    (SN_FEATURES=conv_wgroup=0)."""
+    return (s.Cg == s.Kg == 32 and s.C % 32 == 0 and s.R == 3 and s.S == 3
+            and (s.groups > 1 or (s.H, s.W) != _WGROUP_PINNED_DENSE)
+            and s.dh == 1 and s.dw == 1 and s.sh in (1, 2) and s.sw in (1, 2)
+            and max(s.N * s.H * s.W, s.N * s.P * s.Q) < _GROUPED_MAX_PIX and s.P > 0 and s.Q > 0
+            and max(s.C, s.ph, s.pw) <= 1 << 20 and features.enabled("conv_wgroup"))
+
+
+def _wgroup_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
+    k = _lib.kernels()
+    k.sn_conv_wgroup_part_floats.restype = C.c_longlong
+    n = int(k.sn_conv_wgroup_part_floats(*(C.c_longlong(v) for v in (s.N, s.P, s.Q, s.C))))
+    if n <= 0:
+        raise ValueError(f"32-wide grouped weight gradient: unsupported geometry {s}")
     return torch.empty(n, dtype=torch.float32, device=device), n
 
 
@@ -631,6 +663,14 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
         part, n = _grouped_part(s, x.device)
         call(GROUPED_WGRAD, dy2, x, part, n, dw, int(dw_acc), s.N, s.H, s.W, s.C, s.Cg, s.sh, s.sw, s.ph, s.pw)
         return
+    if dw is not None and plan is None and ldd == s.K and ldx == s.C and wgroup_ok(s) and _dw_io_ok(dy2, x):
+        # the group's nine 32 x 32 tap products over slabs of pixels, fixed-order finalize; the bias
+        # gradient stays a column sum
+        if db is not None:
+            colsum(dy2, db, accumulate=db_acc)
+        part, n = _wgroup_part(s, x.device)
+        call(WGROUP_WGRAD, dy2, x, part, n, dw, int(dw_acc), s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
+        return
     if db is not None and not fused_db:
         assert ldd == s.K
         colsum(dy2, db, accumulate=db_acc)
@@ -767,6 +807,11 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out):
     if (ldd == s.K and grouped_ok(s) and ws.fp8_dgrad is None and _dw_io_ok(dy, w, dx, gate)
             and not _side_covers(dx)):
         call(GROUPED_DGRAD, dy, w, gate, dx, s.N, s.H, s.W, s.C, s.Cg, s.sh, s.sw, s.ph, s.pw)
+        return dx
+    if (ldd == s.K and wgroup_ok(s) and ws.fp8_dgrad is None and _dw_io_ok(dy, w, dx, gate)
+            and not _side_covers(dx)):
+        # by output phase: only the taps of a phase's parity are multiplied, no dcol, no col2im
+        call(WGROUP_DGRAD, dy, w, gate, dx, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
         return dx
     if flip:
         # dgrad == forward conv of dy with flipped / transposed weights, pad' = R-1-pad.
