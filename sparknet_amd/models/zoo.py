@@ -14,6 +14,8 @@
   pointwise 1x1 blocks, each conv followed by BatchNorm -> Scale -> ReLU)
 * ``resnext50``      — not in the reference; ResNeXt-50 32x4d (Xie et al. 2017): ResNet-50's stem and
   head around bottlenecks whose 3x3 is a 32-group convolution carrying the stage's stride
+* ``mnasnet``        — not in the reference; MnasNet-B1 (Tan et al. 2019): inverted residuals whose depthwise
+  layers are 3x3 or 5x5, each conv followed by BatchNorm -> Scale [-> ReLU]
 * ``se_resnet50``    — not in the reference; SE-ResNet-50 (Hu et al. 2018): ResNet-50 with a squeeze-and-
   excitation tail per block (global pool, two 1x1 convolutions, Sigmoid) gating the block output in an Axpy
 
@@ -346,6 +348,51 @@ def mobilenet(train_batch=32, test_batch=50, crop=224, classes=1000, alpha=1.0):
     return NetParam("MobileNet", *L)
 
 
+# (output width, depthwise window, stride, expansion, repeats) of MnasNet-B1's inverted-residual stacks
+MNASNET = ((24, 3, 2, 3, 3), (40, 5, 2, 3, 3), (80, 5, 2, 6, 3), (96, 3, 1, 6, 2), (192, 5, 2, 6, 4), (320, 3, 1, 6, 1))
+
+
+def mnasnet(train_batch=32, test_batch=50, crop=224, classes=1000, alpha=1.0):
+    """MnasNet-B1 (Tan et al. 2019, "MnasNet: Platform-Aware Neural Architecture Search for Mobile"):
+    not in the reference.  3x3 / 2 stem to 32 channels, a depthwise 3x3 and a 1x1 to 16, then the
+    MNASNET stacks of inverted residuals — ``blockS_R/expand`` (1x1 to expansion x input width),
+    ``/dw`` (depthwise 3x3: csrc/kernels/conv_dw.hip, or 5x5: csrc/kernels/conv_xdw.hip; carries the
+    stride in a stack's first block; pad (window - 1) / 2) and ``/project`` (1x1, no ReLU), with an
+    Eltwise SUM shortcut ``blockS_R`` where the stride is 1 and the width does not change — a 1x1 to
+    1280, global average ``pool`` (any crop) and the InnerProduct ``fc`` with bias.  Every conv is
+    bias-free with in-place BatchNorm -> Scale [-> ReLU].  4 383 312 learnable elements besides the
+    BatchNorm statistics at alpha = 1, 1000 classes.  ``alpha`` is the width multiplier of every
+    layer but the 1280-wide one; widths stay multiples of 8 (the 16-byte channel lanes of the kernels)."""
+    def width(n):
+        return max(8, int(n * alpha + 4) // 8 * 8)
+
+    def block(name, bottom, k, n, **kw):
+        return _conv_bn(L, name, None, bottom, k, n, names=(name + "/bn", name + "/scale", name + "/relu"), **kw)
+
+    L = list(data_layers(train_batch, test_batch, 3, crop, crop))
+    c = width(32)
+    x = block("stem/conv", "data", 3, c, stride=2, pad=1)
+    x = block("stem/dw", x, 3, c, pad=1, group=c)
+    c = width(16)
+    x = block("stem/sep", x, 1, c, relu=False)
+    for stage, (n, k, stride, expansion, reps) in enumerate(MNASNET, 1):
+        n = width(n)
+        for r in range(1, reps + 1):
+            tag, first = f"block{stage}_{r}", r == 1
+            y = block(tag + "/expand", x, 1, c * expansion)
+            y = block(tag + "/dw", y, k, c * expansion, stride=stride if first else 1, pad=(k - 1) // 2,
+                      group=c * expansion)
+            y = block(tag + "/project", y, 1, n, relu=False)
+            if c == n and (stride == 1 or not first):
+                L.append(EltwiseLayer(tag, [x, y], "SUM"))
+                y = tag
+            x, c = y, n
+    x = block("head/conv", x, 1, 1280)
+    L += [PoolingLayer("pool", [x], Pooling.Ave, global_pooling=True),
+          _ip("fc", "pool", classes, MSRA, _c(0.0)), *_head("fc", top5=True)]
+    return NetParam("MnasNet-B1", *L)
+
+
 def _resnext_block(L, tag, bottom, width, cardinality, stride, project):
     """res{tag}: 1x1 -> grouped 3x3 (stride, ``cardinality`` groups: csrc/kernels/conv_grouped.hip)
     -> 1x1 (x2), summed with the input or its projection."""
@@ -498,6 +545,11 @@ def mobilenet_solver(net=None):
                    display=20, max_iter=500000, momentum=0.9, weight_decay=4e-5)
 
 
+def mnasnet_solver(net=None):  # MobileNet's schedule (the paper trains with RMSProp)
+    return _solver(net or mnasnet(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="poly", power=1.0,
+                   display=20, max_iter=500000, momentum=0.9, weight_decay=4e-5)
+
+
 def resnext50_solver(net=None):  # ResNet-50's schedule
     return _solver(net or resnext50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
                    gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
@@ -515,6 +567,7 @@ MODELS = {
     "vgg16": (vgg16, vgg16_solver), "resnet50": (resnet50, resnet50_solver),
     "resnet_cifar": (resnet_cifar, resnet_cifar_solver), "mobilenet": (mobilenet, mobilenet_solver),
     "resnext50": (resnext50, resnext50_solver), "se_resnet50": (se_resnet50, se_resnet50_solver),
+    "mnasnet": (mnasnet, mnasnet_solver),
 }
 
 

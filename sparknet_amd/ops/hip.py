@@ -254,6 +254,9 @@ def conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=Non
     if direct_io and ldy == s.K and depthwise_ok(s) and _dw_io_ok(x, w, y):
         call("conv_dw_fwd", x, w, b, y, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw, int(relu))
         return y
+    if direct_io and ldy == s.K and xdepthwise_ok(s) and _dw_io_ok(x, w, y):
+        call(XDW_FWD, x, w, b, y, *_xdw_geo(s), int(relu))
+        return y
     if direct_io and ldy == s.K and grouped_ok(s) and _dw_io_ok(x, w, y):
         call(GROUPED_FWD, x, w, b, y, s.N, s.H, s.W, s.C, s.Cg, s.sh, s.sw, s.ph, s.pw, int(relu))
         return y
@@ -385,6 +388,41 @@ def _dw_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
     n = int(k.sn_conv_dw_part_floats(*(C.c_longlong(v) for v in (s.N, s.P, s.Q, s.C))))
     if n <= 0:
         raise ValueError(f"depthwise weight gradient: unsupported geometry {s}")
+    return torch.empty(n, dtype=torch.float32, device=device), n
+
+
+XDW_FWD, XDW_WGRAD, XDW_DGRAD = "conv_xdw_fwd", "conv_xdw_wgrad", "conv_xdw_dgrad"
+XDW_MAX_EXTENT = 7  # largest dilated window extent per axis
+
+
+def xdepthwise_ok(s: ConvSpec) -> bool:
+    """Depthwise convolutions with wide or dilated windows that the patch-resident kernels take
+    (csrc/kernels/conv_xdw.hip: MnasNet's 5x5, 7x7, dilated 3x3, 1x7): one filter per channel
+    (groups == C == K), whole 8-channel lanes, dilated extents (R - 1) dh + 1 and (S - 1) dw + 1 of at
+    most 7, strides 1 or 2 per axis, dilation only with both strides 1, any pad, inside the limits of
+    the kernels' 32-bit pixel arithmetic (sn_conv_xdw_*'s geometry check).  The undilated 3x3 window
+    is never taken: it belongs to depthwise_ok and conv_dw.hip, also with that switch off.  A channel
+    multiplier, C % 8 != 0, larger extents and dilation with a stride keep the per-group path.  The
+    switch is read on every call (SN_FEATURES=conv_depthwise_wide=0)."""
+    eh, ew = (s.R - 1) * s.dh + 1, (s.S - 1) * s.dw + 1
+    return (s.groups == s.C == s.K and s.C % 8 == 0 and s.R >= 1 and s.S >= 1 and s.dh >= 1 and s.dw >= 1
+            and eh <= XDW_MAX_EXTENT and ew <= XDW_MAX_EXTENT
+            and not (s.R == 3 and s.S == 3 and s.dh == 1 and s.dw == 1) and not depthwise_ok(s)
+            and s.sh in (1, 2) and s.sw in (1, 2) and ((s.dh == 1 and s.dw == 1) or (s.sh == 1 and s.sw == 1))
+            and max(s.N * s.H * s.W, s.N * s.P * s.Q) < _GROUPED_MAX_PIX and s.P > 0 and s.Q > 0
+            and max(s.C, s.ph, s.pw) <= 1 << 20 and features.enabled("conv_depthwise_wide"))
+
+
+def _xdw_geo(s: ConvSpec) -> tuple:
+    return (s.N, s.H, s.W, s.C, s.R, s.S, s.sh, s.sw, s.ph, s.pw, s.dh, s.dw)
+
+
+def _xdw_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
+    k = _lib.kernels()
+    k.sn_conv_xdw_part_floats.restype = C.c_longlong
+    n = int(k.sn_conv_xdw_part_floats(*(C.c_longlong(v) for v in _xdw_geo(s))))
+    if n <= 0:
+        raise ValueError(f"wide depthwise weight gradient: unsupported geometry {s}")
     return torch.empty(n, dtype=torch.float32, device=device), n
 
 
@@ -655,6 +693,13 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
         call("conv_dw_wgrad", dy2, x, part, n, dw, 0 if dw is None else 1 + int(dw_acc),
              db, 0 if db is None else 1 + int(db_acc), s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
         return
+    if ((dw is not None or db is not None) and plan is None and ldd == s.K and ldx == s.C and xdepthwise_ok(s)
+            and _dw_io_ok(dy2, x)):
+        # the taps split over a block's waves, x patch and dy tile in LDS, slab partials, fixed-order finalize
+        part, n = _xdw_part(s, x.device)
+        call(XDW_WGRAD, dy2, x, part, n, dw, 0 if dw is None else 1 + int(dw_acc),
+             db, 0 if db is None else 1 + int(db_acc), *_xdw_geo(s))
+        return
     if dw is not None and plan is None and ldd == s.K and ldx == s.C and grouped_ok(s) and _dw_io_ok(dy2, x):
         # per-bundle tap products over slabs of pixels, fixed-order finalize; the bias gradient
         # stays a column sum
@@ -841,6 +886,11 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out):
         return dx
     if ldd == s.K and depthwise_ok(s) and _dw_io_ok(dy, w, dx, gate) and not _side_covers(dx):
         call("conv_dw_dgrad", dy, w, gate, dx, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
+        return dx
+    if (ldd == s.K and xdepthwise_ok(s) and ws.fp8_dgrad is None and _dw_io_ok(dy, w, dx, gate)
+            and not _side_covers(dx)):
+        # gathered from the dy patch in LDS; at stride 2 only the taps of the pixel's parity
+        call(XDW_DGRAD, dy, w, gate, dx, *_xdw_geo(s))
         return dx
     if (ldd == s.K and ldo == s.C and tstride_ok(s) and ws.fp8_dgrad is None and _dw_io_ok(dy, w, dx, gate)
             and not _side_covers(dx)):

@@ -37,6 +37,7 @@ DEFAULTS = {
     "conv_packed_k64": True,    # tap-packed <3, 64> instance (VGG-16 conv1_1 after its fold)
     "conv_direct_fp8": True,    # e4m3 direct conv for fp8 layers
     "conv_depthwise": True,     # per-channel kernels for depthwise 3x3 convs (0: one im2col + GEMM per group)
+    "conv_depthwise_wide": True,  # patch-resident kernels for depthwise convs with 5x5, 7x7 or dilated windows (0: one im2col + GEMM per group)
     "conv_grouped": True,       # 16-channel bundle kernels for narrow-group 3x3 convs, Cg == Kg in {4, 8, 16} (0: implicit grouped GEMM / per-group loop)
     "conv_wgroup": True,        # dense per-group MFMA kernels for 3x3 convs with Cg == Kg == 32 (ResNeXt stage 5; 0: implicit grouped GEMM, generic stride-2 data gradient)
     "conv_patch": True,         # patch-resident data gradient of 5x5 grouped convs, 128 -> 48 channels per group (CaffeNet conv2; 0: implicit grouped GEMM)
