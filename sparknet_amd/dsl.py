@@ -230,6 +230,13 @@ def AxpyLayer(name, bottom, *, top=None):
     return _base("Axpy", name, bottom, top)
 
 
+def ShuffleChannelLayer(name, bottom, group, *, top=None):
+    """ShuffleNet's channel shuffle: the channels as ``group`` rows of C / group, transposed."""
+    lp = _base("ShuffleChannel", name, bottom, top)
+    lp.shuffle_channel_param.group = group
+    return lp
+
+
 def SigmoidLayer(name, bottom, *, top=None, in_place=False):
     return _base("Sigmoid", name, bottom, list(bottom) if in_place else top)
 
@@ -294,5 +301,6 @@ scale_layer = ScaleLayer
 bias_layer = BiasLayer
 eltwise_layer = EltwiseLayer
 axpy_layer = AxpyLayer
+shuffle_channel_layer = ShuffleChannelLayer
 sigmoid_layer = SigmoidLayer
 net_param = NetParam

@@ -1338,6 +1338,39 @@ class BiasLayer(_BroadcastLayer):
             self.bias = self._add_coef(p.filler if p.HasField("filler") else None, 0.0)
 
 
+@register("ShuffleChannel")
+class ShuffleChannelLayer(Layer):
+    """The channel shuffle of ShuffleNet (Zhang et al. 2018; shuffle_channel_layer of the public Caffe
+    release): the C channels, read as ``group`` rows of C / group, are transposed, so that the next
+    grouped convolution's groups each see channels of every group of the last:
+    ``top[:, j * group + i] = bottom[:, i * (C / group) + j]``.  One bottom, one top, not in place, no
+    parameters; the backward pass is the shuffle with C / group groups.  4-D and 2-D blobs (the channel
+    is their innermost stored axis).  GPU: shuffle_channel_k (csrc/kernels/conv_gpw.hip), one launch
+    each way; CPU and the fp32 device mode: the reshape / transpose of ops.ref."""
+    exact_bottoms = 1
+    exact_tops = 1
+
+    def layer_setup(self, bottoms, tops):
+        self.group = int(self.lp.shuffle_channel_param.group)
+
+    def reshape(self, bottoms, tops):
+        b = bottoms[0]
+        if len(b.shape) not in (2, 4) or self.group < 1 or b.shape[1] % self.group != 0:
+            raise ValueError(f"ShuffleChannel {self.name!r}: a 2-D or 4-D bottom whose {b.shape[1:2]} channels split "
+                             f"into group = {self.group} whole groups is needed, got shape {tuple(b.shape)}")
+        if tops[0] is b:
+            raise ValueError(f"ShuffleChannel {self.name!r} cannot run in place")
+        tops[0].reshape(b.shape, b.dtype)
+
+    def forward(self, bottoms, tops):
+        tops[0].data = ops.shuffle_channels(bottoms[0].data, self.group)
+
+    def backward(self, tops, propagate_down, bottoms):
+        if propagate_down[0]:
+            b = bottoms[0]
+            b.diff = ops.shuffle_channels(tops[0].diff, b.shape[1] // self.group).to(b.dtype)
+
+
 @register("Axpy")
 class AxpyLayer(Layer):
     """The tail of a squeeze-and-excitation block (axpy_layer of the SENet release, Hu et al.

@@ -16,6 +16,8 @@
   head around bottlenecks whose 3x3 is a 32-group convolution carrying the stage's stride
 * ``mnasnet``        — not in the reference; MnasNet-B1 (Tan et al. 2019): inverted residuals whose depthwise
   layers are 3x3 or 5x5, each conv followed by BatchNorm -> Scale [-> ReLU]
+* ``shufflenet``     — not in the reference; ShuffleNet v1 (Zhang et al. 2018): units of grouped 1x1, ShuffleChannel,
+  depthwise 3x3 and grouped 1x1, summed with the input or concatenated with its average pooling
 * ``se_resnet50``    — not in the reference; SE-ResNet-50 (Hu et al. 2018): ResNet-50 with a squeeze-and-
   excitation tail per block (global pool, two 1x1 convolutions, Sigmoid) gating the block output in an Axpy
 
@@ -28,7 +30,8 @@ from __future__ import annotations
 from .. import proto
 from ..dsl import (AccuracyLayer, AxpyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer,
                    Include, InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer,
-                   ScaleLayer, SigmoidLayer, SoftmaxWithLoss)
+                   ScaleLayer, ShuffleChannelLayer, SigmoidLayer, SoftmaxWithLoss)
+from ..ops.spec import PoolSpec
 
 WB = [(1.0, 1.0), (2.0, 0.0)]   # weight / bias lr & decay mults used by the ImageNet models
 W12 = [{"lr_mult": 1.0}, {"lr_mult": 2.0}]
@@ -393,6 +396,66 @@ def mnasnet(train_batch=32, test_batch=50, crop=224, classes=1000, alpha=1.0):
     return NetParam("MnasNet-B1", *L)
 
 
+# widths of ShuffleNet v1's three stages by the number of groups (Zhang et al. 2018, table 1), and their units
+SHUFFLENET_WIDTHS = {1: (144, 288, 576), 2: (200, 400, 800), 3: (240, 480, 960), 4: (272, 544, 1088),
+                     8: (384, 768, 1536)}
+SHUFFLENET_UNITS = (4, 8, 4)
+
+
+def shufflenet(groups=3, scale=1.0, train_batch=32, test_batch=50, crop=224, classes=1000):
+    """ShuffleNet v1 (Zhang et al. 2018, "ShuffleNet: An Extremely Efficient Convolutional Neural
+    Network for Mobile Devices"): not in the reference.  ``conv1`` 3x3 / 2 to 24 channels and a 3x3 / 2
+    max ``pool1``, then three stages of 4 / 8 / 4 units at SHUFFLENET_WIDTHS[groups] channels.  Unit
+    ``resxN``: ``_conv1`` grouped 1x1 to a quarter of the stage width (ungrouped in the very first
+    unit, whose input has 24 channels) with ReLU, ``shuffleN`` (ShuffleChannel), ``_conv2`` depthwise
+    3x3 carrying the unit's stride, ``_conv3`` grouped 1x1 (csrc/kernels/conv_gpw.hip for both 1x1
+    layers), then at stride 1 ``_elewise``, an Eltwise SUM with the unit's input, and at stride 2 (a
+    stage's first unit) ``_concat`` with ``_match_conv``, a 3x3 / 2 average pooling of the input, where
+    ``_conv3`` makes width - input channels; ReLU after either.  The pooling's pad (0 or 1) is the one
+    at which Caffe's ceil-mode output size equals the depthwise layer's.  Global average ``pool_ave``
+    (any crop) and the InnerProduct ``fc1000`` with bias.  Every conv is bias-free with in-place
+    BatchNorm -> Scale [-> ReLU].  1 865 728 learnable elements besides the BatchNorm statistics at
+    groups = 3, scale = 1, 1000 classes.  ``scale`` is the paper's width multiplier of the stages:
+    scaled widths are rounded to multiples of 16 x groups, so that the channels per group of every
+    grouped 1x1 stay multiples of 4 (what the kernels take; at scale 1 that holds for groups 1, 3, 8)."""
+    def width(n):
+        q = 16 * groups
+        return n if scale == 1.0 else max(q, int(n * scale / q + 0.5) * q)
+
+    def block(name, bottom, k, n, **kw):
+        return _conv_bn(L, name, None, bottom, k, n, names=(name + "_bn", name + "_scale", name + "_relu"), **kw)
+
+    L = list(data_layers(train_batch, test_batch, 3, crop, crop))
+    x, c = block("conv1", "data", 3, 24, stride=2, pad=1), 24
+    L.append(_pool("pool1", x, 3, 2))
+    x, h = "pool1", PoolSpec(1, (crop - 1) // 2 + 1, 1, 1, 3, 1, 2, 1).P
+    unit = 0
+    for stage, reps in enumerate(SHUFFLENET_UNITS):
+        n = width(SHUFFLENET_WIDTHS[groups][stage])
+        for r in range(reps):
+            unit += 1
+            tag, first = f"resx{unit}", r == 0
+            y = block(tag + "_conv1", x, 1, n // 4, group=1 if unit == 1 else groups)
+            L.append(ShuffleChannelLayer(f"shuffle{unit}", [y], groups))
+            y = block(tag + "_conv2", f"shuffle{unit}", 3, n // 4, stride=2 if first else 1, pad=1, group=n // 4,
+                      relu=False)
+            y = block(tag + "_conv3", y, 1, n - c if first else n, group=groups, relu=False)
+            if first:
+                h2 = (h - 1) // 2 + 1  # the depthwise 3x3 / 2 with pad 1
+                pad = next(p for p in (0, 1) if PoolSpec(1, h, 1, 1, 3, 1, 2, 1, p, 0).P == h2)
+                L += [_pool(tag + "_match_conv", x, 3, 2, ave=True, pad=pad),
+                      ConcatLayer(tag + "_concat", [tag + "_match_conv", y])]
+                x, h = tag + "_concat", h2
+            else:
+                L.append(EltwiseLayer(tag + "_elewise", [x, y], "SUM"))
+                x = tag + "_elewise"
+            L.append(_relu(x + "_relu", x))
+            c = n
+    L += [PoolingLayer("pool_ave", [x], Pooling.Ave, global_pooling=True),
+          _ip(f"fc{classes}", "pool_ave", classes, MSRA, _c(0.0)), *_head(f"fc{classes}", top5=True)]
+    return NetParam(f"ShuffleNet-{scale:g}x-g{groups}", *L)
+
+
 def _resnext_block(L, tag, bottom, width, cardinality, stride, project):
     """res{tag}: 1x1 -> grouped 3x3 (stride, ``cardinality`` groups: csrc/kernels/conv_grouped.hip)
     -> 1x1 (x2), summed with the input or its projection."""
@@ -550,6 +613,11 @@ def mnasnet_solver(net=None):  # MobileNet's schedule (the paper trains with RMS
                    display=20, max_iter=500000, momentum=0.9, weight_decay=4e-5)
 
 
+def shufflenet_solver(net=None):  # the paper's linear decay, as MobileNet's schedule here
+    return _solver(net or shufflenet(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="poly", power=1.0,
+                   display=20, max_iter=500000, momentum=0.9, weight_decay=4e-5)
+
+
 def resnext50_solver(net=None):  # ResNet-50's schedule
     return _solver(net or resnext50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
                    gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
@@ -567,7 +635,7 @@ MODELS = {
     "vgg16": (vgg16, vgg16_solver), "resnet50": (resnet50, resnet50_solver),
     "resnet_cifar": (resnet_cifar, resnet_cifar_solver), "mobilenet": (mobilenet, mobilenet_solver),
     "resnext50": (resnext50, resnext50_solver), "se_resnet50": (se_resnet50, se_resnet50_solver),
-    "mnasnet": (mnasnet, mnasnet_solver),
+    "mnasnet": (mnasnet, mnasnet_solver), "shufflenet": (shufflenet, shufflenet_solver),
 }
 
 

@@ -78,6 +78,7 @@ lrn_forward = _dispatch("lrn_forward")
 lrn_backward = _dispatch("lrn_backward")
 relu_forward = _dispatch("relu_forward")
 relu_backward = _dispatch("relu_backward")
+shuffle_channels = _dispatch("shuffle_channels")
 softmax_forward = _dispatch("softmax_forward")
 softmax_backward = _dispatch("softmax_backward")
 accuracy = _dispatch("accuracy")

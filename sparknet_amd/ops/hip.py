@@ -263,6 +263,9 @@ def conv_forward(x, w, b, s: ConvSpec, relu=False, ws=None, folded=None, out=Non
     if direct_io and ldy == s.K and wgroup_ok(s) and _dw_io_ok(x, w, y):
         call(WGROUP_FWD, x, w, b, y, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw, int(relu))
         return y
+    if direct_io and ldy == s.K and gpw_ok(s) and _dw_io_ok(x, w, y):
+        call(GPW_FWD, x, w, b, y, M, s.groups, s.Cg, s.Kg, int(relu))
+        return y
     if _implicit_ok(s):
         kred = s.R * s.S * s.Cg
         A = Im2col(x, _geom(s, ldx), kcontig=True, gstride=s.Cg)
@@ -479,6 +482,47 @@ def _wgroup_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
     n = int(k.sn_conv_wgroup_part_floats(*(C.c_longlong(v) for v in (s.N, s.P, s.Q, s.C))))
     if n <= 0:
         raise ValueError(f"32-wide grouped weight gradient: unsupported geometry {s}")
+    return torch.empty(n, dtype=torch.float32, device=device), n
+
+
+GPW_FWD, GPW_DGRAD, GPW_WGRAD = "conv_gpw_fwd", "conv_gpw_dgrad", "conv_gpw_wgrad"
+GPW_WGRAD_FINALIZE = "conv_gpw_wgrad_finalize"
+GPW_MAX_WIDTH = 1024      # channels per group on either side
+GPW_LDS = 160 * 1024      # a block's weights, source tile and output tile
+GRAD_STORE, GRAD_ACC = 1, 2
+
+
+def _gpw_lds(nr: int, no: int) -> int:
+    """LDS bytes of the forward / data-gradient kernel for nr reduced and no output channels per group
+    (io_lds of csrc/kernels/conv_gpw.hip): [16 OF][64 RS + 16] weights, a 64-row source tile of the
+    same row length, a 64-row output tile and the bias."""
+    rsb, of = 64 * -(-nr // 32) + 16, -(-no // 16)
+    return (16 * of + 64) * rsb + 64 * (32 * of + 16) + 64 * of
+
+
+def gpw_ok(s: ConvSpec) -> bool:
+    """Grouped pointwise convolutions the per-group MFMA kernels take (csrc/kernels/conv_gpw.hip:
+    ShuffleNet): 1x1 window, stride 1, pad 0, no dilation, at least two groups, Cg and Kg multiples of
+    4 (free to differ) of at most GPW_MAX_WIDTH, the group's weights and one tile within the LDS in
+    both directions, inside the limits of the kernels'
+    32-bit row arithmetic (sn_conv_gpw_*'s geometry check).  Other windows, strided or dilated
+    pointwise layers, ungrouped layers and Cg or Kg % 4 != 0 keep the implicit grouped GEMM or the
+    per-group path.  The switch is read on every call (SN_FEATURES=conv_gpw=0)."""
+    M = s.N * s.H * s.W
+    return (s.groups >= 2 and s.R == 1 and s.S == 1 and _unit_conv(s) and s.ph == 0 and s.pw == 0
+            and s.C == s.groups * s.Cg and s.K == s.groups * s.Kg
+            and s.Cg % 4 == 0 and s.Kg % 4 == 0 and 0 < s.Cg <= GPW_MAX_WIDTH and 0 < s.Kg <= GPW_MAX_WIDTH
+            and max(_gpw_lds(s.Cg, s.Kg), _gpw_lds(s.Kg, s.Cg)) <= GPW_LDS
+            and s.groups <= 65535
+            and 0 < M < _GROUPED_MAX_PIX and s.groups * -(-M // 64) < 2 ** 31 and features.enabled("conv_gpw"))
+
+
+def _gpw_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
+    k = _lib.kernels()
+    k.sn_conv_gpw_part_floats.restype = C.c_longlong
+    n = int(k.sn_conv_gpw_part_floats(*(C.c_longlong(v) for v in (s.N * s.H * s.W, s.groups, s.Cg, s.Kg))))
+    if n <= 0:
+        raise ValueError(f"grouped pointwise weight gradient: unsupported geometry {s}")
     return torch.empty(n, dtype=torch.float32, device=device), n
 
 
@@ -716,6 +760,15 @@ def _conv_wgrad(dy2, x, s, M, kred, plan, fused_db, dw, db, ws, dw_acc, db_acc, 
         part, n = _wgroup_part(s, x.device)
         call(WGROUP_WGRAD, dy2, x, part, n, dw, int(dw_acc), s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
         return
+    if dw is not None and plan is None and ldd == s.K and ldx == s.C and gpw_ok(s) and _dw_io_ok(dy2, x):
+        # dy_g^T x_g per group over slabs of rows, both operands read transposed from the staged tiles,
+        # fixed-order finalize; the bias gradient stays a column sum
+        if db is not None:
+            colsum(dy2, db, accumulate=db_acc)
+        part, n = _gpw_part(s, x.device)
+        call(GPW_WGRAD, dy2, x, part, n, M, s.groups, s.Cg, s.Kg)
+        call(GPW_WGRAD_FINALIZE, part, n, dw, GRAD_ACC if dw_acc else GRAD_STORE, M, s.groups, s.Cg, s.Kg)
+        return
     if db is not None and not fused_db:
         assert ldd == s.K
         colsum(dy2, db, accumulate=db_acc)
@@ -857,6 +910,11 @@ def _conv_dgrad(dy, x, w, s, M, gate, ws, dyq, ldd, ldx, dx_out):
             and not _side_covers(dx)):
         # by output phase: only the taps of a phase's parity are multiplied, no dcol, no col2im
         call(WGROUP_DGRAD, dy, w, gate, dx, s.N, s.H, s.W, s.C, s.sh, s.sw, s.ph, s.pw)
+        return dx
+    if (ldd == s.K and dx_out is None and gpw_ok(s) and ws.fp8_dgrad is None and _dw_io_ok(dy, w, dx, gate)
+            and not _side_covers(dx)):
+        # the forward's kernel with the group's weights staged transposed: no flip pass
+        call(GPW_DGRAD, dy, w, gate, dx, M, s.groups, s.Cg, s.Kg)
         return dx
     if flip:
         # dgrad == forward conv of dy with flipped / transposed weights, pad' = R-1-pad.
@@ -1306,6 +1364,24 @@ def cast_f32_to_bf16(src, dst):
 
 def advance_rng(rng_state):
     call("advance_rng", rng_state)
+
+
+SHUFFLE_MAX_C = 16384  # a row of the channel shuffle must fit its 32 KB of LDS
+
+
+def shuffle_channels(x, groups: int):
+    """ShuffleNet's channel shuffle on the NHWC storage (shuffle_channel_k, csrc/kernels/conv_gpw.hip):
+    ``y[..., j * groups + i] = x[..., i * (C // groups) + j]``.  Its backward is the same call with
+    ``C // groups`` groups.  bf16 only; the fp32 device mode uses the reference formula."""
+    x = _c(x)
+    Cc = x.shape[-1]
+    if x.dtype != BF16 or groups < 1 or Cc % groups != 0 or Cc > SHUFFLE_MAX_C:
+        raise ValueError(f"shuffle_channels: bf16 rows of at most {SHUFFLE_MAX_C} channels in whole groups, got "
+                         f"{x.dtype} {tuple(x.shape)} groups={groups}")
+    y = torch.empty_like(x)
+    if x.numel():
+        call("shuffle_channel", x, y, x.numel() // Cc, Cc, groups)
+    return y
 
 
 def concat_channels(parts, out):

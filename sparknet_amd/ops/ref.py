@@ -230,6 +230,15 @@ def lrn_backward(dy, x, size, alpha, beta, k, within=False, y=None):
 
 # --- neurons (relu/sigmoid/tanh/... layers) --------------------------------------------
 
+def shuffle_channels(x, groups: int):
+    """Channel shuffle on the channels-last storage: ``y[..., j * groups + i] = x[..., i * (C // groups) + j]``
+    (the reshape (groups, C / groups) -> transpose -> flatten of the ShuffleNet release)."""
+    Cc = x.shape[-1]
+    if groups < 1 or Cc % groups != 0:
+        raise ValueError(f"shuffle_channels: {Cc} channels do not split into {groups} groups")
+    return x.reshape(*x.shape[:-1], groups, Cc // groups).transpose(-1, -2).reshape(x.shape).contiguous()
+
+
 def relu_forward(x, slope=0.0):
     xf = x.float()
     return torch.where(xf > 0, xf, xf * slope).to(x.dtype)

@@ -115,6 +115,7 @@ MESSAGES: dict[str, tuple[dict, list]] = {
         o("power_param", 122, "PowerParameter"), o("prelu_param", 131, "PReLUParameter"),
         o("python_param", 130, "PythonParameter"), o("reduction_param", 136, "ReductionParameter"),
         o("relu_param", 123, "ReLUParameter"), o("reshape_param", 133, "ReshapeParameter"),
+        o("shuffle_channel_param", 164, "ShuffleChannelParameter"),  # this project's own field number
         o("sigmoid_param", 124, "SigmoidParameter"), o("softmax_param", 125, "SoftmaxParameter"),
         o("spp_param", 132, "SPPParameter"), o("slice_param", 126, "SliceParameter"),
         o("tanh_param", 127, "TanHParameter"), o("threshold_param", 128, "ThresholdParameter"),
@@ -203,6 +204,7 @@ MESSAGES: dict[str, tuple[dict, list]] = {
     "ReshapeParameter": ({}, [o("shape", 1, "BlobShape"), o("axis", 2, "int32", 0), o("num_axes", 3, "int32", -1)]),
     "SigmoidParameter": ({"Engine": ENGINE}, [o("engine", 1, "SigmoidParameter.Engine", "DEFAULT")]),
     "SliceParameter": ({}, [o("axis", 3, "int32", 1), r("slice_point", 2, "uint32"), o("slice_dim", 1, "uint32", 1)]),
+    "ShuffleChannelParameter": ({}, [o("group", 1, "uint32", 1)]),
     "SoftmaxParameter": ({"Engine": ENGINE}, [o("engine", 1, "SoftmaxParameter.Engine", "DEFAULT"),
                                               o("axis", 2, "int32", 1)]),
     "TanHParameter": ({"Engine": ENGINE}, [o("engine", 1, "TanHParameter.Engine", "DEFAULT")]),
