@@ -93,6 +93,27 @@ def ConvolutionLayer(name, bottom, kernel, numOutput, *, stride=None, pad=None, 
     return lp
 
 
+def DeconvolutionLayer(name, bottom, kernel, numOutput, *, stride=None, pad=None, group=1, top=None,
+                       weight_filler=None, bias_filler=None, param=None, bias_term=True):
+    """Transposed convolution; ``group == numOutput == bottom channels`` with a ``bilinear`` filler is the
+    learned upsampling of the segmentation nets (csrc/kernels/conv_updw.hip)."""
+    lp = ConvolutionLayer(name, bottom, kernel, numOutput, stride=stride, pad=pad, group=group, top=top,
+                          weight_filler=weight_filler, bias_filler=bias_filler, param=param, bias_term=bias_term)
+    lp.type = "Deconvolution"
+    return lp
+
+
+def CropLayer(name, bottom, offset=(), *, axis=2, top=None):
+    """``bottom[0]`` cut to ``bottom[1]``'s extent from ``axis`` on, starting at ``offset`` (an int for all
+    cropped axes, or one per axis)."""
+    lp = _base("Crop", name, bottom, top)
+    if axis != 2:
+        lp.crop_param.axis = axis
+    lp.crop_param.offset.extend([offset] if isinstance(offset, int) else list(offset))
+    lp.crop_param.SetInParent()
+    return lp
+
+
 def PoolingLayer(name, bottom, pooling=Pooling.Max, kernel=(2, 2), stride=(1, 1), *, pad=None, top=None,
                  global_pooling=False):
     lp = _base("Pooling", name, bottom, top)
@@ -302,5 +323,7 @@ bias_layer = BiasLayer
 eltwise_layer = EltwiseLayer
 axpy_layer = AxpyLayer
 shuffle_channel_layer = ShuffleChannelLayer
+deconvolution_layer = DeconvolutionLayer
+crop_layer = CropLayer
 sigmoid_layer = SigmoidLayer
 net_param = NetParam

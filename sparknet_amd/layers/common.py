@@ -1371,6 +1371,51 @@ class ShuffleChannelLayer(Layer):
             b.diff = ops.shuffle_channels(tops[0].diff, b.shape[1] // self.group).to(b.dtype)
 
 
+@register("Crop")
+class CropLayer(Layer):
+    """Crop (crop_layer.cpp of upstream Caffe; the reference snapshot predates it): ``bottom[0]`` is cut to
+    the extent of ``bottom[1]`` on every axis from ``crop_param.axis`` (default 2) on, starting at
+    ``crop_param.offset`` — none (0), one for all cropped axes, or one per cropped axis.  A window past
+    the source is a construction error.  The gradient goes to ``bottom[0]`` alone: the top gradient inside
+    the window, zero outside.  4-D bf16 blobs on the GPU: crop_k each way on the NHWC storage, the
+    backward writing the whole bottom gradient in one pass (csrc/kernels/conv_updw.hip); other blobs, the
+    CPU and the fp32 device mode: tensor slicing (ops.ref)."""
+    exact_bottoms = 2
+    exact_tops = 1
+
+    def reshape(self, bottoms, tops):
+        a, ref_shape = bottoms[0], bottoms[1].shape
+        p = self.lp.crop_param
+        nd = len(a.shape)
+        axis = a.canonical_axis(int(p.axis))
+        offs = [int(o) for o in p.offset]
+        if not 0 <= axis < nd or len(ref_shape) != nd:
+            raise ValueError(f"Crop {self.name!r}: axis {p.axis} / bottoms of {nd} and {len(ref_shape)} axes")
+        if len(offs) > 1 and len(offs) != nd - axis:
+            raise ValueError(f"Crop {self.name!r}: {len(offs)} offsets for {nd - axis} cropped axes")
+        if tops[0] is a:
+            raise ValueError(f"Crop {self.name!r} cannot run in place")
+        self.offsets, shape = [0] * nd, list(a.shape)
+        for i in range(axis, nd):
+            o = (offs[i - axis] if len(offs) > 1 else offs[0]) if offs else 0
+            if o < 0 or o + ref_shape[i] > a.shape[i]:
+                raise ValueError(f"Crop {self.name!r}: axis {i}: offset {o} + extent {ref_shape[i]} exceeds the "
+                                 f"source's {a.shape[i]}")
+            self.offsets[i], shape[i] = o, ref_shape[i]
+        tops[0].reshape(shape, a.dtype)
+
+    def _stored(self, v):  # per-axis values in the order of the stored layout: NCHW -> NHWC for 4-D blobs
+        return [v[0], v[2], v[3], v[1]] if len(v) == 4 else list(v)
+
+    def forward(self, bottoms, tops):
+        tops[0].data = ops.crop_window(bottoms[0].data, self._stored(self.offsets), self._stored(tops[0].shape))
+
+    def backward(self, tops, propagate_down, bottoms):
+        if propagate_down[0]:
+            b = bottoms[0]
+            b.diff = ops.crop_window_backward(tops[0].diff, self._stored(self.offsets), self._stored(b.shape)).to(b.dtype)
+
+
 @register("Axpy")
 class AxpyLayer(Layer):
     """The tail of a squeeze-and-excitation block (axpy_layer of the SENet release, Hu et al.

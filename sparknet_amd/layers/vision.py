@@ -426,7 +426,9 @@ class ConvolutionLayer(Layer):
 class DeconvolutionLayer(Layer):
     """Transposed convolution (deconv_layer.cpp).  Weight Caffe shape (C_in, K/g, R, S).
     Forward = conv dgrad, backward = conv forward + wgrad with roles swapped; runs
-    through the reference path on CPU and the same GEMM engine on GPU."""
+    through the reference path on CPU and the same GEMM engine on GPU.  A depthwise layer
+    (group == num_output == bottom channels: learned upsampling) inside hip.updw_ok runs the
+    upsampling kernels of csrc/kernels/conv_updw.hip on a bf16 GPU net instead."""
     min_bottoms = 1
     min_tops = 1
 
@@ -469,9 +471,21 @@ class DeconvolutionLayer(Layer):
         # deconv weight (C, R, S, K/g) == conv weight of top->bottom conv: (Cout=C, R, S, Cin_g=K/g)
         return self.weight.compute
 
+    def _updw(self, b, s) -> bool:
+        """The depthwise upsampling kernels (csrc/kernels/conv_updw.hip) serve this bottom: a bf16 GPU
+        net outside the fp32 device mode and a geometry inside hip.updw_ok."""
+        if not (b.data.is_cuda and b.data.dtype == torch.bfloat16 and not ops.f32_active()):
+            return False
+        from ..ops import hip
+        return self.weight.compute.dtype == torch.bfloat16 and hip.updw_ok(s)
+
     def forward(self, bottoms, tops):
         for b, t in zip(bottoms, tops):
             s = self.fwd_spec(b)
+            if self._updw(b, s):  # one launch, bias inside, every output pixel written once
+                bias = self.bias.data if self.bias is not None else None
+                t.data = ops.deconv_dw_forward(b.data, self._w_as_conv(), bias, s).to(t.dtype)
+                continue
             zeros = torch.zeros(t.data.shape, dtype=t.dtype, device=t.device)
             y = ops.conv_backward(b.data, zeros, self._w_as_conv(), s, True, None, None)
             if self.bias is not None:
@@ -482,6 +496,12 @@ class DeconvolutionLayer(Layer):
         dw = self.weight.diff if self.param_grads_needed(0) else None
         for i, (t, b) in enumerate(zip(tops, bottoms)):
             s = self.fwd_spec(b)
+            if self._updw(b, s):  # weight and bias gradient in one pass, accumulated as below
+                db = self.bias.diff if (self.bias is not None and self.param_grads_needed(1)) else None
+                dx = ops.deconv_dw_backward(t.diff, b.data, self._w_as_conv(), s, bool(propagate_down[i]), dw, db)
+                if propagate_down[i]:
+                    b.diff = dx.to(b.dtype)
+                continue
             if self.bias is not None and self.param_grads_needed(1):
                 self.bias.diff += t.diff.float().reshape(-1, self.K).sum(0)
             if dw is not None:

@@ -18,6 +18,8 @@
   layers are 3x3 or 5x5, each conv followed by BatchNorm -> Scale [-> ReLU]
 * ``shufflenet``     — not in the reference; ShuffleNet v1 (Zhang et al. 2018): units of grouped 1x1, ShuffleChannel,
   depthwise 3x3 and grouped 1x1, summed with the input or concatenated with its average pooling
+* ``fcn8s``          — not in the reference; FCN-8s (Long et al. 2015): the VGG-16 trunk, convolutional fc6 / fc7,
+  three depthwise Deconvolution upsamplings fused with cropped pool4 / pool3 scores
 * ``se_resnet50``    — not in the reference; SE-ResNet-50 (Hu et al. 2018): ResNet-50 with a squeeze-and-
   excitation tail per block (global pool, two 1x1 convolutions, Sigmoid) gating the block output in an Axpy
 
@@ -30,7 +32,7 @@ from __future__ import annotations
 from .. import proto
 from ..dsl import (AccuracyLayer, AxpyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer,
                    Include, InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer,
-                   ScaleLayer, ShuffleChannelLayer, SigmoidLayer, SoftmaxWithLoss)
+                   ScaleLayer, ShuffleChannelLayer, SigmoidLayer, SoftmaxWithLoss, CropLayer, DeconvolutionLayer)
 from ..ops.spec import PoolSpec
 
 WB = [(1.0, 1.0), (2.0, 0.0)]   # weight / bias lr & decay mults used by the ImageNet models
@@ -250,6 +252,56 @@ def vgg16(train_batch=64, test_batch=50, crop=224, classes=1000):
           _ip("fc7", "fc6", 4096, _g(0.005), _c(0.1)), _relu("relu7", "fc7"), DropoutLayer("drop7", ["fc7"], 0.5),
           _ip("fc8", "fc7", classes, _g(0.01), _c(0.0)), *_head("fc8", top5=True)]
     return NetParam("VGG_ILSVRC_16_layers", *L)
+
+
+def fcn8s(classes=21, train_batch=1, test_batch=1, crop=500, width=1.0):
+    """FCN-8s (Long, Shelhamer, Darrell 2015, "Fully Convolutional Networks for Semantic Segmentation";
+    layer names of the public voc-fcn8s net): not in the reference.  The VGG-16 trunk with ``conv1_1``
+    padded by 100, ``fc6`` as a 7x7 and ``fc7`` as a 1x1 convolution with dropout, the class scores
+    ``score_fr``, then three learned upsamplings — depthwise Deconvolution layers (group = classes, no
+    bias, ``bilinear`` filler: csrc/kernels/conv_updw.hip): ``upscore2`` (4x4 / 2) fused (Eltwise SUM)
+    with ``score_pool4`` cropped at offset 5, ``upscore_pool4`` (4x4 / 2) fused with ``score_pool3``
+    cropped at offset 9, and ``upscore8`` (16x16 / 8, lr_mult 0) cropped against ``data`` at offset 31 to
+    ``score``.  SoftmaxWithLoss over the channel axis with ignore_label 255, not normalised; the label
+    is [N, 1, crop, crop].  ``width`` scales the trunk's channel counts (rounded to multiples of 8),
+    ``fc6`` / ``fc7`` included.  At crop 500: fc6 16 x 16, upscore2 34, upscore_pool4 70, upscore8 568."""
+    ch = lambda n: max(8, int(n * width / 8 + 0.5) * 8)
+    L = [RDDLayer("data", [train_batch, 3, crop, crop], Include.Train),
+         RDDLayer("label", [train_batch, 1, crop, crop], Include.Train),
+         RDDLayer("data", [test_batch, 3, crop, crop], Include.Test),
+         RDDLayer("label", [test_batch, 1, crop, crop], Include.Test)]
+    x = "data"
+    for stage, (n, reps) in enumerate([(64, 2), (128, 2), (256, 3), (512, 3), (512, 3)], 1):
+        for r in range(1, reps + 1):
+            name = f"conv{stage}_{r}"
+            L += [_conv(name, x, 3, ch(n), pad=100 if x == "data" else 1, wf=MSRA, bf=_c(0.0)),
+                  _relu(f"relu{stage}_{r}", name)]
+            x = name
+        L.append(_pool(f"pool{stage}", x, 2, 2))
+        x = f"pool{stage}"
+    L += [_conv("fc6", x, 7, ch(4096), wf=MSRA, bf=_c(0.0)), _relu("relu6", "fc6"), DropoutLayer("drop6", ["fc6"], 0.5),
+          _conv("fc7", "fc6", 1, ch(4096), wf=MSRA, bf=_c(0.0)), _relu("relu7", "fc7"),
+          DropoutLayer("drop7", ["fc7"], 0.5), _conv("score_fr", "fc7", 1, classes, wf=MSRA, bf=_c(0.0))]
+
+    def up(name, bottom, f, lr):
+        return DeconvolutionLayer(name, [bottom], (2 * f - f % 2,) * 2, classes, stride=f, group=classes,
+                                  weight_filler={"type": "bilinear"}, param=[(lr, lr)], bias_term=False)
+
+    def skip(pool, bottom, offset, fuse):
+        L.extend([_conv(f"score_{pool}", pool, 1, classes, wf=MSRA, bf=_c(0.0)),
+                  CropLayer(f"score_{pool}c", [f"score_{pool}", bottom], offset),
+                  EltwiseLayer(fuse, [bottom, f"score_{pool}c"], "SUM")])
+        return fuse
+
+    L.append(up("upscore2", "score_fr", 2, 1.0))
+    x = skip("pool4", "upscore2", 5, "fuse_pool4")
+    L.append(up("upscore_pool4", x, 2, 1.0))
+    x = skip("pool3", "upscore_pool4", 9, "fuse_pool3")
+    loss = SoftmaxWithLoss("loss", ["score", "label"])
+    loss.loss_param.ignore_label = 255
+    loss.loss_param.normalize = False
+    L += [up("upscore8", x, 8, 0.0), CropLayer("score", ["upscore8", "data"], 31), loss]
+    return NetParam("voc-fcn8s", *L)
 
 
 MSRA = {"type": "msra"}
@@ -618,6 +670,11 @@ def shufflenet_solver(net=None):  # the paper's linear decay, as MobileNet's sch
                    display=20, max_iter=500000, momentum=0.9, weight_decay=4e-5)
 
 
+def fcn8s_solver(net=None):  # the public voc-fcn8s solver: fixed rate on the unnormalised loss, high momentum
+    return _solver(net or fcn8s(), test_iter=[736], test_interval=999999999, base_lr=1e-14, lr_policy="fixed",
+                   display=20, max_iter=100000, momentum=0.99, weight_decay=5e-4)
+
+
 def resnext50_solver(net=None):  # ResNet-50's schedule
     return _solver(net or resnext50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
                    gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
@@ -636,6 +693,7 @@ MODELS = {
     "resnet_cifar": (resnet_cifar, resnet_cifar_solver), "mobilenet": (mobilenet, mobilenet_solver),
     "resnext50": (resnext50, resnext50_solver), "se_resnet50": (se_resnet50, se_resnet50_solver),
     "mnasnet": (mnasnet, mnasnet_solver), "shufflenet": (shufflenet, shufflenet_solver),
+    "fcn8s": (fcn8s, fcn8s_solver),
 }
 
 

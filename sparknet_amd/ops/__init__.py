@@ -84,6 +84,42 @@ softmax_backward = _dispatch("softmax_backward")
 accuracy = _dispatch("accuracy")
 
 
+def deconv_dw_forward(x, w, bias, s):
+    """Depthwise Deconvolution forward with the bias inside (``s``: the convolution top -> bottom).  bf16
+    GPU tensors run conv_updw_fwd; the CPU and the fp32 device mode keep the data-gradient route."""
+    if _gpu(x):
+        return _hipmod().deconv_dw_forward(x, w, bias, s)
+    zeros = torch.zeros((s.N, s.H, s.W, s.C), dtype=x.dtype, device=x.device)
+    y = conv_backward(x, zeros, w, s, True, None, None)
+    return y if bias is None else (y.float() + bias.float()).to(y.dtype)
+
+
+def deconv_dw_backward(dy, x, w, s, need_dx, dw=None, db=None, dw_acc=True, db_acc=True):
+    """Backward of deconv_dw_forward: dw, db (stored or accumulated) and the bottom gradient or None."""
+    if _gpu(dy):
+        return _hipmod().deconv_dw_backward(dy, x, w, s, need_dx, dw, db, dw_acc, db_acc)
+    if db is not None:
+        g = dy.float().reshape(-1, s.C).sum(0)
+        db.copy_(db + g if db_acc else g)
+    if dw is not None:
+        conv_backward(x, dy, w, s, False, dw, None, dw_acc=dw_acc)
+    return conv_forward(dy, w, None, s) if need_dx else None
+
+
+def crop_window(x, offsets, shape):
+    """Crop forward on the stored layout: ``x[o0:o0 + s0, o1:o1 + s1, ...]`` (crop_k for 4-D bf16 GPU blobs)."""
+    if _gpu(x) and x.dim() == 4 and x.dtype == torch.bfloat16:
+        return _hipmod().crop_window(x, offsets, shape)
+    return ref.crop_window(x, offsets, shape)
+
+
+def crop_window_backward(dy, offsets, shape):
+    """Gradient of crop_window for a source of ``shape``: dy inside the window, zero outside."""
+    if _gpu(dy) and dy.dim() == 4 and dy.dtype == torch.bfloat16:
+        return _hipmod().crop_window_backward(dy, offsets, shape)
+    return ref.crop_window_backward(dy, offsets, shape)
+
+
 def pool_backward(dy, x, s, aux=None, y=None, gate=False):
     """gate=True: x is a slope-0 in-place ReLU output whose backward is fused here (MAX
     pooling on the GPU encodes it in the forward's argmax mask)."""

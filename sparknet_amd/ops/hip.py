@@ -526,8 +526,96 @@ def _gpw_part(s: ConvSpec, device) -> tuple[torch.Tensor, int]:
     return torch.empty(n, dtype=torch.float32, device=device), n
 
 
+UPDW_FWD, UPDW_DGRAD, UPDW_WGRAD = "conv_updw_fwd", "conv_updw_dgrad", "conv_updw_wgrad"
+UPDW_MAX_WINDOW, UPDW_MAX_STRIDE = 16, 8
+
+
+def updw_ok(s: ConvSpec) -> bool:
+    """Depthwise transposed convolutions the upsampling kernels take (csrc/kernels/conv_updw.hip: FCN's
+    bilinear-initialised Deconvolution layers).  ``s`` is the equivalent convolution top -> bottom of
+    DeconvolutionLayer.fwd_spec: s.H, s.W the layer's output, s.P, s.Q its input.  One filter per channel
+    (groups == C == K), strides 1..8 per axis (free to differ), windows 1..16 per axis, any pad that
+    leaves a positive output, no dilation, any channel count (21 included), bf16 tensors outside the fp32
+    device mode, inside the limits of the kernels' 32-bit pixel arithmetic (sn_conv_updw_*'s geometry
+    check).  Everything else — FCN-32s' 64 x 64 / 32, ungrouped or multi-channel groups, the N-d form,
+    fp8 — keeps its route.  The switch is read on every call (SN_FEATURES=deconv_dw=0)."""
+    return (s.groups == s.C == s.K and s.C >= 1 and s.dh == 1 and s.dw == 1
+            and 1 <= s.sh <= UPDW_MAX_STRIDE and 1 <= s.sw <= UPDW_MAX_STRIDE
+            and 1 <= s.R <= UPDW_MAX_WINDOW and 1 <= s.S <= UPDW_MAX_WINDOW
+            and s.N > 0 and s.H > 0 and s.W > 0 and s.P > 0 and s.Q > 0 and s.ph >= 0 and s.pw >= 0
+            and s.H == (s.P - 1) * s.sh + s.R - 2 * s.ph and s.W == (s.Q - 1) * s.sw + s.S - 2 * s.pw
+            and max(s.N * s.H * s.W, s.N * s.P * s.Q) < _GROUPED_MAX_PIX and max(s.C, s.ph, s.pw) < 1 << 20
+            and features.enabled("deconv_dw"))
+
+
+def _updw_geo(s: ConvSpec) -> tuple:
+    return (s.N, s.P, s.Q, s.C, s.R, s.S, s.sh, s.sw, s.ph, s.pw)
+
+
+def deconv_dw_forward(x, w, bias, s: ConvSpec):
+    """Top [N, H, W, C] of a depthwise Deconvolution from its bottom ``x`` [N, P, Q, C], the weights
+    [C, R, S, 1] (bf16) and the fp32 bias or None: one launch that writes every output pixel once."""
+    if not updw_ok(s):
+        raise ValueError(f"deconv_dw_forward: not a depthwise upsampling geometry: {s}")
+    x, w = as_bf16(x), _c(w)
+    if w.dtype != BF16 or tuple(x.shape) != (s.N, s.P, s.Q, s.C) or w.numel() != s.C * s.R * s.S:
+        raise ValueError(f"deconv_dw_forward: x {tuple(x.shape)} / w {tuple(w.shape)} {w.dtype} do not fit {s}")
+    if bias is not None:
+        bias = _c(bias.float())
+    y = torch.empty((s.N, s.H, s.W, s.C), dtype=BF16, device=x.device)
+    call(UPDW_FWD, x, w, bias, y, *_updw_geo(s))
+    return y
+
+
+def deconv_dw_backward(dy, x, w, s: ConvSpec, need_dx: bool, dw=None, db=None, dw_acc=True, db_acc=True):
+    """Backward of deconv_dw_forward from the top gradient ``dy`` [N, H, W, C]: the fp32 weight gradient
+    ``dw`` [C, R, S, 1] and bias gradient ``db`` [C] (stored or accumulated; either may be None) in one
+    pass plus a fixed-order finalize, and the bottom gradient [N, P, Q, C] when ``need_dx``."""
+    if not updw_ok(s):
+        raise ValueError(f"deconv_dw_backward: not a depthwise upsampling geometry: {s}")
+    dy, w = as_bf16(dy), _c(w)
+    if w.dtype != BF16 or tuple(dy.shape) != (s.N, s.H, s.W, s.C):
+        raise ValueError(f"deconv_dw_backward: dy {tuple(dy.shape)} / w {w.dtype} do not fit {s}")
+    if dw is not None or db is not None:
+        x = as_bf16(x)
+        for t in (dw, db):
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("deconv_dw_backward: the gradients are contiguous fp32 tensors")
+        k = _lib.kernels()
+        k.sn_conv_updw_part_floats.restype = C.c_longlong
+        n = int(k.sn_conv_updw_part_floats(*(C.c_longlong(v) for v in _updw_geo(s))))
+        if n <= 0:
+            raise ValueError(f"depthwise upsampling weight gradient: unsupported geometry {s}")
+        part = torch.empty(n, dtype=torch.float32, device=dy.device)
+        call(UPDW_WGRAD, dy, x, part, n, dw, 0 if dw is None else 1 + int(dw_acc),
+             db, 0 if db is None else 1 + int(db_acc), *_updw_geo(s))
+    if not need_dx:
+        return None
+    dx = torch.empty((s.N, s.P, s.Q, s.C), dtype=BF16, device=dy.device)
+    call(UPDW_DGRAD, dy, w, dx, *_updw_geo(s))
+    return dx
+
+
+def crop_window(x, offsets, shape):
+    """The Crop layer's forward on the NHWC storage: the window of ``x`` [N, H, W, C] at ``offsets``
+    (n, h, w, c) with ``shape`` (n, h, w, c), one launch of crop_k (csrc/kernels/conv_updw.hip)."""
+    x = as_bf16(x)
+    y = torch.empty(tuple(shape), dtype=BF16, device=x.device)
+    call("crop", x, y, *x.shape, *shape, *offsets, 0)
+    return y
+
+
+def crop_window_backward(dy, offsets, shape):
+    """Gradient of crop_window for a source of ``shape`` (N, H, W, C): ``dy`` inside the window, zero
+    outside, the whole tensor written by one launch (no separate clear)."""
+    dy = as_bf16(dy)
+    dx = torch.empty(tuple(shape), dtype=BF16, device=dy.device)
+    call("crop", dy, dx, *shape, *dy.shape, *offsets, 1)
+    return dx
+
+
 PATCH_DGRAD = "conv_patch_dgrad"
-PATCH_MIN_ROWS, PATCH_MAX_COLS = 8, 32  # a 256-pixel band of at most 32 columns has at least 8 rows
+PATCH_MIN_ROWS,PATCH_MAX_COLS = 8, 32  # a 256-pixel band of at most 32 columns has at least 8 rows
 
 
 def patch_dgrad_ok(s: ConvSpec) -> bool:

@@ -239,6 +239,18 @@ def shuffle_channels(x, groups: int):
     return x.reshape(*x.shape[:-1], groups, Cc // groups).transpose(-1, -2).reshape(x.shape).contiguous()
 
 
+def crop_window(x, offsets, shape):
+    """The window of ``x`` at ``offsets`` with ``shape``, one entry per stored axis (crop_layer.cpp)."""
+    return x[tuple(slice(o, o + n) for o, n in zip(offsets, shape))].contiguous()
+
+
+def crop_window_backward(dy, offsets, shape):
+    """Gradient of crop_window for a source of ``shape``: dy inside the window, zero outside."""
+    dx = torch.zeros(tuple(shape), dtype=dy.dtype, device=dy.device)
+    dx[tuple(slice(o, o + n) for o, n in zip(offsets, dy.shape))] = dy
+    return dx
+
+
 def relu_forward(x, slope=0.0):
     xf = x.float()
     return torch.where(xf > 0, xf, xf * slope).to(x.dtype)

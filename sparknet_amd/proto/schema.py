@@ -112,6 +112,7 @@ MESSAGES: dict[str, tuple[dict, list]] = {
         o("inner_product_param", 117, "InnerProductParameter"), o("log_param", 134, "LogParameter"),
         o("lrn_param", 118, "LRNParameter"), o("memory_data_param", 119, "MemoryDataParameter"),
         o("mvn_param", 120, "MVNParameter"), o("pooling_param", 121, "PoolingParameter"),
+        o("crop_param", 144, "CropParameter"),
         o("power_param", 122, "PowerParameter"), o("prelu_param", 131, "PReLUParameter"),
         o("python_param", 130, "PythonParameter"), o("reduction_param", 136, "ReductionParameter"),
         o("relu_param", 123, "ReLUParameter"), o("reshape_param", 133, "ReshapeParameter"),
@@ -201,6 +202,7 @@ MESSAGES: dict[str, tuple[dict, list]] = {
         o("coeff", 3, "float", 1.0)]),
     "ReLUParameter": ({"Engine": ENGINE}, [o("negative_slope", 1, "float", 0),
                                            o("engine", 2, "ReLUParameter.Engine", "DEFAULT")]),
+    "CropParameter": ({}, [o("axis", 1, "int32", 2), r("offset", 2, "uint32")]),
     "ReshapeParameter": ({}, [o("shape", 1, "BlobShape"), o("axis", 2, "int32", 0), o("num_axes", 3, "int32", -1)]),
     "SigmoidParameter": ({"Engine": ENGINE}, [o("engine", 1, "SigmoidParameter.Engine", "DEFAULT")]),
     "SliceParameter": ({}, [o("axis", 3, "int32", 1), r("slice_point", 2, "uint32"), o("slice_dim", 1, "uint32", 1)]),

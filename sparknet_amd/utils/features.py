@@ -41,6 +41,7 @@ DEFAULTS = {
     "conv_grouped": True,       # 16-channel bundle kernels for narrow-group 3x3 convs, Cg == Kg in {4, 8, 16} (0: implicit grouped GEMM / per-group loop)
     "conv_wgroup": True,        # dense per-group MFMA kernels for 3x3 convs with Cg == Kg == 32 (ResNeXt stage 5; 0: implicit grouped GEMM, generic stride-2 data gradient)
     "conv_gpw": True,           # per-group MFMA kernels for grouped 1x1 convs, Cg and Kg multiples of 4 (ShuffleNet; 0: implicit grouped GEMM / per-group loop)
+    "deconv_dw": True,          # upsampling kernels for depthwise Deconvolution layers, strides up to 8, windows up to 16, any C (FCN; 0: per-channel dcol GEMM + col2im loop)
     "conv_patch": True,         # patch-resident data gradient of 5x5 grouped convs, 128 -> 48 channels per group (CaffeNet conv2; 0: implicit grouped GEMM)
     "conv_tstride": True,       # phase-decomposed data gradient of dense stride-2 convs, windows up to 4x4 (0: fp32 dcol GEMM + col2im)
     # per-image, per-channel kernels (csrc/kernels/se.hip)
