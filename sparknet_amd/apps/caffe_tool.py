@@ -46,6 +46,12 @@ def _fill_inputs(net: Net, seed=0):
                     t.set_nchw(torch.randn(t.shape, generator=g) * 50)
                 else:
                     t.data.copy_(torch.randint(0, 10, tuple(t.data.shape), generator=g).float())
+    for li, layer in enumerate(net.layers):  # ROIs: boxes inside the image, dealt round-robin to the images
+        if layer.type_name in ("ROIPooling", "ROIAlign"):
+            feat, rois = net.bottom_vecs[li]
+            R, extent = rois.shape[0], torch.tensor([feat.shape[3], feat.shape[2]]) / layer.scale
+            p = (torch.rand(R, 2, 2, generator=g) * extent).sort(dim=1).values
+            rois.data.copy_(torch.cat([torch.arange(R).reshape(R, 1) % feat.shape[0], p[:, 0], p[:, 1]], 1))
 
 
 class _Timer:
@@ -76,7 +82,10 @@ class _Timer:
 def cmd_time(args):
     dev = _device(args)
     if args.zoo:
-        netp = models.build(args.zoo, train_batch=args.batch, test_batch=args.batch)
+        if args.zoo == "fast_rcnn":  # its batch is the image count; --trunk picks the CaffeNet or VGG-16 trunk
+            netp = models.build(args.zoo, images=args.batch, trunk=args.trunk)
+        else:
+            netp = models.build(args.zoo, train_batch=args.batch, test_batch=args.batch)
     else:
         netp = proto.read_net(args.model)
     phase = proto.TRAIN if args.phase.upper() == "TRAIN" else proto.TEST
@@ -164,6 +173,7 @@ def main(argv=None):
     p.add_argument("--model")
     p.add_argument("--zoo")
     p.add_argument("--batch", type=int, default=64)
+    p.add_argument("--trunk", default="caffenet")
     p.add_argument("--weights")
     p.add_argument("--snapshot")
     p.add_argument("--iterations", type=int, default=50)

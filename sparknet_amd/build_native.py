@@ -46,11 +46,12 @@ HIP_FLAGS = [
 # fp32 VALU forms (v_pk_{add,mul,fma}_f32) as a precaution: the compiler emits none for it today
 # with or without the flag, no result was seen to differ, and the flag keeps a later edit of its
 # epilogue from bringing them in unnoticed.  conv_wgroup.hip, conv_xdw.hip, conv_gpw.hip and conv_updw.hip follow it.  The older
-# files are built as they always were.
+# files are built as they always were.  roi.hip also turns contraction off: its bin edges and sample
+# positions are defined by their fp32 order of operations, so no product may fuse into a following sum.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_TU_FLAGS = {"conv_tstride.hip": _NO_PACKED_FP32, "conv_wgroup.hip": _NO_PACKED_FP32,
                 "conv_xdw.hip": _NO_PACKED_FP32, "conv_gpw.hip": _NO_PACKED_FP32,
-                "conv_updw.hip": _NO_PACKED_FP32}
+                "conv_updw.hip": _NO_PACKED_FP32, "roi.hip": _NO_PACKED_FP32 + ["-ffp-contract=off"]}
 # host C++ runtime: g++ against the HIP runtime API (hipHostMalloc / hipMemcpyAsync /
 # events); the HIP platform macro selects the AMD backend of the runtime headers.
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall", f"-I{CSRC / 'runtime'}",

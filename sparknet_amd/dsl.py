@@ -258,6 +258,37 @@ def ShuffleChannelLayer(name, bottom, group, *, top=None):
     return lp
 
 
+def ROIPoolingLayer(name, bottom, pooled, spatial_scale=1.0, *, top=None):
+    """Fast R-CNN's ROIPooling of ``bottom = [features, rois]`` into ``pooled = (h, w)`` bins per ROI."""
+    lp = _base("ROIPooling", name, bottom, top)
+    p = lp.roi_pooling_param
+    p.pooled_h, p.pooled_w = pooled
+    p.spatial_scale = spatial_scale
+    return lp
+
+
+def ROIAlignLayer(name, bottom, pooled, spatial_scale=1.0, sampling_ratio=0, *, top=None):
+    """ROIAlign (aligned = false) of ``bottom = [features, rois]``; ``sampling_ratio`` 0 is adaptive."""
+    lp = _base("ROIAlign", name, bottom, top)
+    p = lp.roi_align_param
+    p.pooled_h, p.pooled_w = pooled
+    p.spatial_scale = spatial_scale
+    if sampling_ratio:
+        p.sampling_ratio = sampling_ratio
+    return lp
+
+
+def SmoothL1LossLayer(name, bottom, sigma=1.0, *, loss_weight=None, top=None):
+    """``bottom = [pred, target[, inside_w[, outside_w]]]``."""
+    lp = _base("SmoothL1Loss", name, bottom, top)
+    lp.smooth_l1_loss_param.SetInParent()
+    if sigma != 1.0:
+        lp.smooth_l1_loss_param.sigma = sigma
+    if loss_weight is not None:
+        lp.loss_weight.append(loss_weight)
+    return lp
+
+
 def SigmoidLayer(name, bottom, *, top=None, in_place=False):
     return _base("Sigmoid", name, bottom, list(bottom) if in_place else top)
 
@@ -325,5 +356,8 @@ axpy_layer = AxpyLayer
 shuffle_channel_layer = ShuffleChannelLayer
 deconvolution_layer = DeconvolutionLayer
 crop_layer = CropLayer
+roi_pooling_layer = ROIPoolingLayer
+roi_align_layer = ROIAlignLayer
+smooth_l1_loss_layer = SmoothL1LossLayer
 sigmoid_layer = SigmoidLayer
 net_param = NetParam

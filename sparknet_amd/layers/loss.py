@@ -451,3 +451,47 @@ class ContrastiveLossLayer(LossLayer, _RowLossGPU):
             if propagate_down[i]:
                 g = sign * lw * coef * self.diff
                 bottoms[i].diff = g.reshape(bottoms[i].data.shape).to(bottoms[i].dtype)
+
+
+@register("SmoothL1Loss")
+class SmoothL1LossLayer(LossLayer):
+    """SmoothL1Loss (smooth_L1_loss_layer.cu of the Fast / Faster R-CNN forks): bottoms ``pred, target[,
+    inside_w[, outside_w]]`` of one element count.  d = inside_w (pred - target); f(d) = 0.5 sigma^2 d^2 below
+    1 / sigma^2, else |d| - 0.5 / sigma^2; loss = sum(outside_w f) / num, num the first axis of ``pred``.  With
+    three bottoms the third is both weights, as in Fast R-CNN.  The gradient goes to ``pred`` and, when
+    requested, negated to ``target``; the weights get none.  GPU: smooth_l1_fwd_k with a fixed-order sum and
+    smooth_l1_bwd_k (csrc/kernels/roi.hip), the loss weight read on the device."""
+    max_bottoms = 4
+
+    def layer_setup(self, bottoms, tops):
+        self.sigma = float(self.lp.smooth_l1_loss_param.sigma)
+        if not self.sigma > 0:
+            raise ValueError(f"SmoothL1Loss {self.name!r}: sigma = {self.sigma} must be positive")
+
+    def reshape(self, bottoms, tops):
+        super().reshape(bottoms, tops)
+        if not bottoms[0].shape or any(b.count != bottoms[0].count for b in bottoms[1:]):
+            raise ValueError(f"SmoothL1Loss {self.name!r}: the bottoms' element counts differ: "
+                             f"{[tuple(b.shape) for b in bottoms]}")
+
+    def allow_force_backward(self, bottom_id: int) -> bool:
+        return bottom_id == 0
+
+    def _operands(self, bottoms):
+        in_w = bottoms[2].data if len(bottoms) > 2 else None
+        out_w = bottoms[3].data if len(bottoms) > 3 else in_w
+        return bottoms[0].data, bottoms[1].data, in_w, out_w
+
+    def forward(self, bottoms, tops):
+        tops[0].data = ops.smooth_l1_forward(*self._operands(bottoms), self.sigma).reshape(())
+
+    def backward(self, tops, propagate_down, bottoms):
+        if any(propagate_down[2:]):
+            raise ValueError(f"SmoothL1Loss {self.name!r} cannot backpropagate to its weights")
+        if not any(propagate_down[:2]):
+            return
+        dp, dt = ops.smooth_l1_backward(*self._operands(bottoms), self.sigma, tops[0].diff, bool(propagate_down[1]))
+        if propagate_down[0]:
+            bottoms[0].diff = dp.reshape(bottoms[0].data.shape).to(bottoms[0].dtype)
+        if propagate_down[1]:
+            bottoms[1].diff = dt.reshape(bottoms[1].data.shape).to(bottoms[1].dtype)

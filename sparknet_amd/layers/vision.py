@@ -906,5 +906,86 @@ class Im2colNdLayer(_NdGeometry, Layer):
         _store_logical(b, dx, diff=True)
 
 
+class _ROILayer(Layer):
+    """Shared shape handling of the region-of-interest layers: bottoms ``[features [N, C, H, W], rois [R, 5]]``
+    with a ROI as (batch index, x1, y1, x2, y2) in image coordinates, top ``[R, C, PH, PW]`` in the features'
+    dtype, not in place; the gradient goes to the features alone.  A ROI whose batch index is not in [0, N)
+    gives zeros and no gradient (upstream aborts; a kernel cannot)."""
+    exact_bottoms = 2
+    exact_tops = 1
+
+    def _param(self):
+        raise NotImplementedError
+
+    def layer_setup(self, bottoms, tops):
+        p = self._param()
+        self.ph, self.pw, self.scale = int(p.pooled_h), int(p.pooled_w), float(p.spatial_scale)
+        if self.ph <= 0 or self.pw <= 0 or not self.scale > 0:
+            raise ValueError(f"{self.type_name} {self.name!r}: pooled_h = {self.ph}, pooled_w = {self.pw} and "
+                             f"spatial_scale = {self.scale} must be positive")
+
+    def reshape(self, bottoms, tops):
+        b, rois = bottoms
+        if len(b.shape) != 4 or len(rois.shape) != 2 or rois.shape[1] != 5 or rois.shape[0] < 1:
+            raise ValueError(f"{self.type_name} {self.name!r}: bottoms of shape [N, C, H, W] and [R, 5] are needed, "
+                             f"got {tuple(b.shape)} and {tuple(rois.shape)}")
+        if tops[0] is b:
+            raise ValueError(f"{self.type_name} {self.name!r} cannot run in place")
+        tops[0].reshape((rois.shape[0], b.shape[1], self.ph, self.pw), b.dtype)
+
+    def allow_force_backward(self, bottom_id: int) -> bool:
+        return bottom_id == 0
+
+    def _check(self, propagate_down):
+        if len(propagate_down) > 1 and propagate_down[1]:
+            raise ValueError(f"{self.type_name} {self.name!r} cannot backpropagate to the ROIs")
+
+
+@register("ROIPooling")
+class ROIPoolingLayer(_ROILayer):
+    """ROIPooling (roi_pooling_layer.cu of the Fast / Faster R-CNN forks): the maximum over each of PH x PW
+    bins of the ROI's rounded box, with upstream's fp32 bin edges.  bf16 GPU nets: roi_pool_fwd_k and the
+    deterministic gather backward roi_pool_bwd_k (csrc/kernels/roi.hip), capturable; elsewhere ops.ref."""
+
+    def _param(self):
+        return self.lp.roi_pooling_param
+
+    def forward(self, bottoms, tops):
+        y, self.argmax = ops.roi_pool_forward(bottoms[0].data, bottoms[1].data, self.ph, self.pw, self.scale)
+        tops[0].data = y.to(tops[0].dtype)
+
+    def backward(self, tops, propagate_down, bottoms):
+        self._check(propagate_down)
+        if propagate_down[0]:
+            b = bottoms[0]
+            b.diff = ops.roi_pool_backward(tops[0].diff, bottoms[1].data, self.argmax, tuple(b.data.shape), self.ph,
+                                           self.pw, self.scale).to(b.dtype)
+
+
+@register("ROIAlign")
+class ROIAlignLayer(_ROILayer):
+    """ROIAlign (Detectron / Caffe2 RoIAlign, aligned = false): the mean of ``sampling_ratio`` squared (0:
+    ceil(roi / pooled) per axis) bilinear samples per bin of the unrounded box.  bf16 GPU nets:
+    roi_align_fwd_k / roi_align_bwd_k (csrc/kernels/roi.hip); elsewhere ops.ref."""
+
+    def _param(self):
+        return self.lp.roi_align_param
+
+    def layer_setup(self, bottoms, tops):
+        super().layer_setup(bottoms, tops)
+        self.sampling = int(self.lp.roi_align_param.sampling_ratio)
+
+    def forward(self, bottoms, tops):
+        y = ops.roi_align_forward(bottoms[0].data, bottoms[1].data, self.ph, self.pw, self.scale, self.sampling)
+        tops[0].data = y.to(tops[0].dtype)
+
+    def backward(self, tops, propagate_down, bottoms):
+        self._check(propagate_down)
+        if propagate_down[0]:
+            b = bottoms[0]
+            b.diff = ops.roi_align_backward(tops[0].diff, bottoms[1].data, tuple(b.data.shape), self.ph, self.pw,
+                                            self.scale, self.sampling).to(b.dtype)
+
+
 __all__ = ["ConvolutionLayer", "DeconvolutionLayer", "PoolingLayer", "LRNLayer", "InnerProductLayer",
-           "Im2colLayer", "POOL_MAX", "POOL_AVE"]
+           "Im2colLayer", "ROIPoolingLayer", "ROIAlignLayer", "POOL_MAX", "POOL_AVE"]

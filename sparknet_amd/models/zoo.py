@@ -20,6 +20,8 @@
   depthwise 3x3 and grouped 1x1, summed with the input or concatenated with its average pooling
 * ``fcn8s``          — not in the reference; FCN-8s (Long et al. 2015): the VGG-16 trunk, convolutional fc6 / fc7,
   three depthwise Deconvolution upsamplings fused with cropped pool4 / pool3 scores
+* ``fast_rcnn``      — not in the reference; Fast R-CNN (Girshick 2015) on the CaffeNet or VGG-16 trunk: ROIPooling
+  (or ROIAlign) of conv5 over given ROIs, fc6 / fc7, a SoftmaxWithLoss and a SmoothL1Loss head
 * ``se_resnet50``    — not in the reference; SE-ResNet-50 (Hu et al. 2018): ResNet-50 with a squeeze-and-
   excitation tail per block (global pool, two 1x1 convolutions, Sigmoid) gating the block output in an Axpy
 
@@ -32,7 +34,8 @@ from __future__ import annotations
 from .. import proto
 from ..dsl import (AccuracyLayer, AxpyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer,
                    Include, InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer,
-                   ScaleLayer, ShuffleChannelLayer, SigmoidLayer, SoftmaxWithLoss, CropLayer, DeconvolutionLayer)
+                   ScaleLayer, ShuffleChannelLayer, SigmoidLayer, SoftmaxWithLoss, CropLayer, DeconvolutionLayer,
+                   ROIAlignLayer, ROIPoolingLayer, SmoothL1LossLayer)
 from ..ops.spec import PoolSpec
 
 WB = [(1.0, 1.0), (2.0, 0.0)]   # weight / bias lr & decay mults used by the ImageNet models
@@ -302,6 +305,53 @@ def fcn8s(classes=21, train_batch=1, test_batch=1, crop=500, width=1.0):
     loss.loss_param.normalize = False
     L += [up("upscore8", x, 8, 0.0), CropLayer("score", ["upscore8", "data"], 31), loss]
     return NetParam("voc-fcn8s", *L)
+
+
+def fast_rcnn(trunk="caffenet", classes=21, images=2, rois=128, size=600, align=False, width=1.0):
+    """Fast R-CNN (Girshick 2015; layer and blob names of the public CaffeNet / VGG16 train nets): not in the
+    reference.  Inputs ``data`` [images, 3, size, size], ``rois`` [rois, 5] as (image, x1, y1, x2, y2),
+    ``labels`` [rois] and ``bbox_targets`` / ``bbox_inside_weights`` / ``bbox_outside_weights`` [rois, 4
+    classes].  The trunk runs to ``conv5`` (CaffeNet) / ``conv5_3`` (VGG-16) without its last pool, its first
+    layers frozen as published; ``roi_pool5`` is a ROIPooling (``align``: ROIAlign, 2 x 2 samples) of 6 x 6
+    (7 x 7 for VGG-16) bins at scale 1 / 16 (csrc/kernels/roi.hip); ``fc6`` / ``fc7`` with dropout feed
+    ``cls_score`` into ``loss_cls`` (SoftmaxWithLoss) and ``bbox_pred`` into ``loss_bbox`` (SmoothL1Loss).
+    ``width`` scales the trunk's and the fc layers' channel counts (rounded to multiples of 8)."""
+    if trunk not in ("caffenet", "vgg16"):
+        raise ValueError(f"fast_rcnn: trunk {trunk!r} is neither 'caffenet' nor 'vgg16'")
+    ch = lambda n: max(8, int(n * width / 8 + 0.5) * 8)
+    frozen = [(0.0, 0.0), (0.0, 0.0)]
+    L = [RDDLayer("data", [images, 3, size, size]), RDDLayer("rois", [rois, 5]), RDDLayer("labels", [rois])]
+    L += [RDDLayer(n, [rois, 4 * classes]) for n in ("bbox_targets", "bbox_inside_weights", "bbox_outside_weights")]
+    if trunk == "caffenet":
+        L += [_conv("conv1", "data", 11, ch(96), stride=4, wf=_g(0.01), bf=_c(0.0), param=frozen),
+              _relu("relu1", "conv1"), _pool("pool1", "conv1", 3, 2), LRNLayer("norm1", ["pool1"], 5, 1e-4, 0.75),
+              _conv("conv2", "norm1", 5, ch(256), pad=2, group=2, wf=_g(0.01), bf=_c(1.0)),
+              _relu("relu2", "conv2"), _pool("pool2", "conv2", 3, 2), LRNLayer("norm2", ["pool2"], 5, 1e-4, 0.75),
+              _conv("conv3", "norm2", 3, ch(384), pad=1, wf=_g(0.01), bf=_c(0.0)), _relu("relu3", "conv3"),
+              _conv("conv4", "conv3", 3, ch(384), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu4", "conv4"),
+              _conv("conv5", "conv4", 3, ch(256), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu5", "conv5")]
+        x, pooled = "conv5", (6, 6)
+    else:
+        x = "data"
+        for stage, (n, reps) in enumerate([(64, 2), (128, 2), (256, 3), (512, 3), (512, 3)], 1):
+            for r in range(1, reps + 1):
+                name = f"conv{stage}_{r}"
+                L += [_conv(name, x, 3, ch(n), pad=1, wf=MSRA, bf=_c(0.0), param=frozen if stage <= 2 else WB),
+                      _relu(f"relu{stage}_{r}", name)]
+                x = name
+            if stage < 5:
+                L.append(_pool(f"pool{stage}", x, 2, 2))
+                x = f"pool{stage}"
+        pooled = (7, 7)
+    L.append(ROIAlignLayer("roi_pool5", [x, "rois"], pooled, 1.0 / 16, 2) if align else
+             ROIPoolingLayer("roi_pool5", [x, "rois"], pooled, 1.0 / 16))
+    L += [_ip("fc6", "roi_pool5", ch(4096), _g(0.005), _c(0.1)), _relu("relu6", "fc6"), DropoutLayer("drop6", ["fc6"], 0.5),
+          _ip("fc7", "fc6", ch(4096), _g(0.005), _c(0.1)), _relu("relu7", "fc7"), DropoutLayer("drop7", ["fc7"], 0.5),
+          _ip("cls_score", "fc7", classes, _g(0.01), _c(0.0)), _ip("bbox_pred", "fc7", 4 * classes, _g(0.001), _c(0.0)),
+          SoftmaxWithLoss("loss_cls", ["cls_score", "labels"], loss_weight=1.0),
+          SmoothL1LossLayer("loss_bbox", ["bbox_pred", "bbox_targets", "bbox_inside_weights", "bbox_outside_weights"],
+                            loss_weight=1.0)]
+    return NetParam("CaffeNet" if trunk == "caffenet" else "VGG_ILSVRC_16_layers", *L)
 
 
 MSRA = {"type": "msra"}
@@ -675,6 +725,11 @@ def fcn8s_solver(net=None):  # the public voc-fcn8s solver: fixed rate on the un
                    display=20, max_iter=100000, momentum=0.99, weight_decay=5e-4)
 
 
+def fast_rcnn_solver(net=None):  # the public Fast R-CNN solvers
+    return _solver(net or fast_rcnn(), base_lr=0.001, lr_policy="step", gamma=0.1, stepsize=30000, display=20,
+                   average_loss=100, max_iter=40000, momentum=0.9, weight_decay=5e-4)
+
+
 def resnext50_solver(net=None):  # ResNet-50's schedule
     return _solver(net or resnext50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
                    gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
@@ -693,7 +748,7 @@ MODELS = {
     "resnet_cifar": (resnet_cifar, resnet_cifar_solver), "mobilenet": (mobilenet, mobilenet_solver),
     "resnext50": (resnext50, resnext50_solver), "se_resnet50": (se_resnet50, se_resnet50_solver),
     "mnasnet": (mnasnet, mnasnet_solver), "shufflenet": (shufflenet, shufflenet_solver),
-    "fcn8s": (fcn8s, fcn8s_solver),
+    "fcn8s": (fcn8s, fcn8s_solver), "fast_rcnn": (fast_rcnn, fast_rcnn_solver),
 }
 
 

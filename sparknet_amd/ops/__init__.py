@@ -120,6 +120,41 @@ def crop_window_backward(dy, offsets, shape):
     return ref.crop_window_backward(dy, offsets, shape)
 
 
+def _roi_hip(x, rois) -> bool:
+    """The ROI kernels (csrc/kernels/roi.hip) serve these tensors; otherwise ops.ref, which reads the ROIs on
+    the host (the CPU, the fp32 device mode, other dtypes, SN_FEATURES=roi_kernels=0)."""
+    return _gpu(x) and _hipmod().roi_ok(x, rois)
+
+
+def roi_pool_forward(x, rois, ph, pw, scale):
+    """ROIPooling forward on the stored layout: (y [R, PH, PW, C], int32 argmax)."""
+    return (_hipmod() if _roi_hip(x, rois) else ref).roi_pool_forward(x, rois, ph, pw, scale)
+
+
+def roi_pool_backward(dy, rois, argmax, x_shape, ph, pw, scale):
+    impl = _hipmod() if _roi_hip(dy, rois) else ref
+    return impl.roi_pool_backward(dy, rois, argmax, x_shape, ph, pw, scale)
+
+
+def roi_align_forward(x, rois, ph, pw, scale, sampling_ratio=0):
+    return (_hipmod() if _roi_hip(x, rois) else ref).roi_align_forward(x, rois, ph, pw, scale, sampling_ratio)
+
+
+def roi_align_backward(dy, rois, x_shape, ph, pw, scale, sampling_ratio=0):
+    impl = _hipmod() if _roi_hip(dy, rois) else ref
+    return impl.roi_align_backward(dy, rois, x_shape, ph, pw, scale, sampling_ratio)
+
+
+def smooth_l1_forward(pred, target, in_w=None, out_w=None, sigma=1.0):
+    """SmoothL1Loss as a 0-d fp32 tensor (smooth_l1_fwd for GPU tensors outside the fp32 device mode)."""
+    return (_hipmod() if _gpu(pred) else ref).smooth_l1_forward(pred, target, in_w, out_w, sigma)
+
+
+def smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_target=False):
+    impl = _hipmod() if _gpu(pred) else ref
+    return impl.smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_target)
+
+
 def pool_backward(dy, x, s, aux=None, y=None, gate=False):
     """gate=True: x is a slope-0 in-place ReLU output whose backward is fused here (MAX
     pooling on the GPU encodes it in the forward's argmax mask)."""

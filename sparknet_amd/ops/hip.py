@@ -614,6 +614,108 @@ def crop_window_backward(dy, offsets, shape):
     return dx
 
 
+ROI_POOL_FWD, ROI_POOL_BWD = "roi_pool_fwd", "roi_pool_bwd"
+ROI_ALIGN_FWD, ROI_ALIGN_BWD = "roi_align_fwd", "roi_align_bwd"
+SMOOTH_L1_FWD, SMOOTH_L1_BWD = "smooth_l1_fwd", "smooth_l1_bwd"
+ROI_CHUNK = 256           # ROIs per staged table chunk of the backward kernels (sn_roi_chunk)
+ROI_MAX_POOLED = 4096     # bins per axis
+ROI_ALIGN_MAX_GRID = 64   # ROIAlign samples per bin and axis
+
+
+def roi_ok(x, rois) -> bool:
+    """Tensors the region-of-interest kernels take (csrc/kernels/roi.hip): a bf16 4-D NHWC ``x``, fp32 ``rois``
+    [R, 5] with R >= 1 on the same device, inside the kernels' 32-bit pixel arithmetic.  The switch is read on
+    every call (SN_FEATURES=roi_kernels=0)."""
+    return (x.dim() == 4 and x.dtype == BF16 and rois.dim() == 2 and rois.shape[1] == 5 and rois.shape[0] >= 1
+            and rois.dtype == torch.float32 and rois.device == x.device and x.numel() > 0
+            and x.shape[0] * x.shape[1] * x.shape[2] < _GROUPED_MAX_PIX and x.shape[3] <= 1 << 20
+            and features.enabled("roi_kernels"))
+
+
+def _roi_args(what, x, rois, shape, ph, pw, scale, sampling_ratio=0):
+    """The kernels' geometry arguments, after the checks that keep them inside their bounds."""
+    if not roi_ok(x, rois):
+        raise ValueError(f"{what}: x {tuple(x.shape)} {x.dtype} / rois {tuple(rois.shape)} {rois.dtype} are not "
+                         f"served by the ROI kernels")
+    R = rois.shape[0]
+    if not (1 <= ph <= ROI_MAX_POOLED and 1 <= pw <= ROI_MAX_POOLED and R * ph * pw < _GROUPED_MAX_PIX
+            and 0 <= sampling_ratio <= ROI_ALIGN_MAX_GRID and 0 < scale <= 1 << 20):
+        raise ValueError(f"{what}: {R} ROIs x {ph} x {pw} bins, scale {scale}, sampling_ratio {sampling_ratio}")
+    return (*shape, R, int(ph), int(pw), float(scale))
+
+
+def roi_pool_forward(x, rois, ph, pw, scale):
+    """ROIPooling of ``x`` [N, H, W, C] over ``rois`` [R, 5]: (y [R, PH, PW, C] bf16, argmax int32)."""
+    x, rois = _c(x), _c(rois)
+    geo = _roi_args("roi_pool_forward", x, rois, x.shape, ph, pw, scale)
+    y = torch.empty((rois.shape[0], ph, pw, x.shape[3]), dtype=BF16, device=x.device)
+    am = torch.empty(y.shape, dtype=torch.int32, device=x.device)
+    call(ROI_POOL_FWD, x, rois, y, am, *geo)
+    return y, am
+
+
+def roi_pool_backward(dy, rois, argmax, x_shape, ph, pw, scale):
+    """Gradient of roi_pool_forward to ``x``: the whole tensor written by one launch, no clear, no atomics."""
+    dy, rois, argmax = as_bf16(dy), _c(rois), _c(argmax)
+    dx = torch.empty(tuple(x_shape), dtype=BF16, device=dy.device)
+    geo = _roi_args("roi_pool_backward", dx, rois, x_shape, ph, pw, scale)
+    if tuple(dy.shape) != (rois.shape[0], ph, pw, x_shape[3]) or argmax.shape != dy.shape or argmax.dtype != torch.int32:
+        raise ValueError(f"roi_pool_backward: dy {tuple(dy.shape)} / argmax {tuple(argmax.shape)} {argmax.dtype}")
+    call(ROI_POOL_BWD, dy, rois, argmax, dx, *geo)
+    return dx
+
+
+def roi_align_forward(x, rois, ph, pw, scale, sampling_ratio=0):
+    """ROIAlign (aligned = false) of ``x`` [N, H, W, C] over ``rois`` [R, 5]: y [R, PH, PW, C] bf16."""
+    x, rois = _c(x), _c(rois)
+    geo = _roi_args("roi_align_forward", x, rois, x.shape, ph, pw, scale, sampling_ratio)
+    y = torch.empty((rois.shape[0], ph, pw, x.shape[3]), dtype=BF16, device=x.device)
+    call(ROI_ALIGN_FWD, x, rois, y, *geo, int(sampling_ratio))
+    return y
+
+
+def roi_align_backward(dy, rois, x_shape, ph, pw, scale, sampling_ratio=0):
+    """Gradient of roi_align_forward to ``x``, in gather form."""
+    dy, rois = as_bf16(dy), _c(rois)
+    dx = torch.empty(tuple(x_shape), dtype=BF16, device=dy.device)
+    geo = _roi_args("roi_align_backward", dx, rois, x_shape, ph, pw, scale, sampling_ratio)
+    if tuple(dy.shape) != (rois.shape[0], ph, pw, x_shape[3]):
+        raise ValueError(f"roi_align_backward: dy {tuple(dy.shape)}")
+    call(ROI_ALIGN_BWD, dy, rois, dx, *geo, int(sampling_ratio))
+    return dx
+
+
+def _smooth_l1_operands(pred, target, in_w, out_w):
+    pred = _c(pred)
+    if pred.dtype not in (BF16, torch.float32) or pred.dim() < 1 or pred.numel() == 0:
+        raise ValueError(f"smooth_l1: pred {tuple(pred.shape)} {pred.dtype}")
+    rest = [None if t is None else _c(t.float()) for t in (target, in_w, out_w)]
+    if any(t is not None and t.numel() != pred.numel() for t in rest) or rest[0] is None:
+        raise ValueError("smooth_l1: target and weights have the element count of pred")
+    return pred, int(pred.dtype == torch.float32), rest
+
+
+def smooth_l1_forward(pred, target, in_w=None, out_w=None, sigma=1.0):
+    """SmoothL1Loss of bf16 / fp32 ``pred`` against fp32 ``target`` with optional inside / outside weights:
+    a 0-d fp32 tensor, per-block partials summed in a fixed order."""
+    pred, f32, (target, in_w, out_w) = _smooth_l1_operands(pred, target, in_w, out_w)
+    part = torch.empty(256, dtype=torch.float32, device=pred.device)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    call(SMOOTH_L1_FWD, pred, f32, target, in_w, out_w, part, loss, pred.numel(), pred.shape[0], float(sigma))
+    return loss
+
+
+def smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_target=False):
+    """(gradient to ``pred`` in its dtype, gradient to ``target`` in fp32 or None); ``loss_weight`` is the
+    0-d fp32 device tensor of the loss top's diff, read by the kernel."""
+    pred, f32, (tgt, in_w, out_w) = _smooth_l1_operands(pred, target, in_w, out_w)
+    lw = _c(loss_weight.float()).reshape(1)
+    dp = torch.empty_like(pred)
+    dt = torch.empty(target.shape, dtype=torch.float32, device=pred.device) if need_target else None
+    call(SMOOTH_L1_BWD, pred, f32, tgt, in_w, out_w, lw, dp, dt, pred.numel(), pred.shape[0], float(sigma))
+    return dp, dt
+
+
 PATCH_DGRAD = "conv_patch_dgrad"
 PATCH_MIN_ROWS,PATCH_MAX_COLS = 8, 32  # a 256-pixel band of at most 32 columns has at least 8 rows
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -249,6 +250,173 @@ def crop_window_backward(dy, offsets, shape):
     dx = torch.zeros(tuple(shape), dtype=dy.dtype, device=dy.device)
     dx[tuple(slice(o, o + n) for o, n in zip(offsets, dy.shape))] = dy
     return dx
+
+
+# --- region-of-interest layers (roi_pooling_layer.cu of the Fast R-CNN fork; Caffe2's RoIAlign) -------------
+# x [N, H, W, C] of any float dtype, rois [R, 5] = (batch index, x1, y1, x2, y2) in image coordinates, y
+# [R, PH, PW, C].  Bin edges and sample positions are computed in float32 in the order of operations of
+# csrc/kernels/roi.hip, which defines them.  A ROI whose batch index is not in [0, N), or with a scaled
+# coordinate that is not finite or beyond 2^20, is ignored: zeros, argmax -1, no gradient.  These functions
+# read the ROIs on the host, so they cannot be captured into a graph.
+
+ROI_COORD_MAX, ROI_ALIGN_MAX_GRID = float(1 << 20), 64
+
+
+def _roi_coords(roi, N, scale):
+    """(image, x1, y1, x2, y2) scaled in float32, or None for an ignored ROI."""
+    c = [roi[k] * np.float32(scale) for k in range(1, 5)]
+    if not 0 <= roi[0] < N or not all(abs(v) <= ROI_COORD_MAX for v in c):
+        return None
+    return (int(roi[0]), *c)
+
+
+def _roi_round(v) -> int:  # half away from zero
+    return int(math.copysign(math.floor(abs(float(v)) + 0.5), float(v)))
+
+
+def _roi_pool_box(roi, N, PH, PW, scale):
+    """(image, first row, first column, bin height, bin width) or None."""
+    c = _roi_coords(roi, N, scale)
+    if c is None:
+        return None
+    n, ws, hs, we, he = c[0], *(_roi_round(v) for v in c[1:])
+    return n, hs, ws, np.float32(max(he - hs + 1, 1)) / np.float32(PH), np.float32(max(we - ws + 1, 1)) / np.float32(PW)
+
+
+def _roi_pool_bin(p, size, start, L):
+    """Bin p of an axis, [lo, hi) clipped to [0, L]."""
+    lo = int(math.floor(np.float32(p) * size)) + start
+    hi = int(math.ceil(np.float32(p + 1) * size)) + start
+    return min(max(lo, 0), L), min(max(hi, 0), L)
+
+
+def roi_pool_forward(x, rois, ph, pw, scale):
+    """ROIPooling: (y, argmax [R, PH, PW, C] int32 holding h * W + w of the maximum, or -1); an empty bin
+    gives 0 / -1, the first maximum in (h, w) order wins a tie."""
+    N, H, W, C = x.shape
+    table = rois.detach().float().cpu().numpy()
+    y = torch.zeros((len(table), ph, pw, C), dtype=x.dtype, device=x.device)
+    am = torch.full((len(table), ph, pw, C), -1, dtype=torch.int32, device=x.device)
+    for r, roi in enumerate(table):
+        box = _roi_pool_box(roi, N, ph, pw, scale)
+        if box is None:
+            continue
+        n, hs, ws, bh, bw = box
+        for i in range(ph):
+            h0, h1 = _roi_pool_bin(i, bh, hs, H)
+            for j in range(pw):
+                w0, w1 = _roi_pool_bin(j, bw, ws, W)
+                if h1 <= h0 or w1 <= w0:
+                    continue
+                win = x[n, h0:h1, w0:w1].reshape(-1, C)
+                m = win.max(0).values
+                first = ((win == m).int().cumsum(0) == 0).sum(0)  # entries before the first maximum
+                y[r, i, j] = m
+                am[r, i, j] = ((h0 + first // (w1 - w0)) * W + w0 + first % (w1 - w0)).int()
+    return y, am
+
+
+def roi_pool_backward(dy, rois, argmax, x_shape, ph, pw, scale):
+    """Gradient of roi_pool_forward to x: dy added at the stored argmax, in (ROI, ph, pw) order."""
+    N, H, W, C = x_shape
+    table = rois.detach().float().cpu().numpy()
+    dx = torch.zeros((N, H * W, C), dtype=torch.float32, device=dy.device)
+    for r, roi in enumerate(table):
+        box = _roi_pool_box(roi, N, ph, pw, scale)
+        if box is None:
+            continue
+        idx = argmax[r].reshape(-1, C).long()
+        dx[box[0]].scatter_add_(0, idx.clamp(min=0), dy[r].reshape(-1, C).float() * (idx >= 0))
+    return dx.reshape(N, H, W, C).to(dy.dtype)
+
+
+def _roi_align_axis(start, size, P, grid, L):
+    """[P, L] float32: the weight each position of an axis of length L has in each of the P bins, summed
+    over the bin's ``grid`` samples (bilinear; zero outside [-1, L], clamped to 0 and L - 1)."""
+    m = np.zeros((P, L), dtype=np.float32)
+    for p in range(P):
+        for i in range(grid):
+            v = start + np.float32(p) * size + (np.float32(i) + np.float32(0.5)) * size / np.float32(grid)
+            if v < -1 or v > L:
+                continue
+            v = max(v, np.float32(0))
+            lo = int(v)
+            if lo >= L - 1:
+                lo = hi = L - 1
+                v = np.float32(lo)
+            else:
+                hi = lo + 1
+            wh = v - np.float32(lo)
+            m[p, lo] += np.float32(1) - wh
+            m[p, hi] += wh
+    return m
+
+
+def _roi_align_weights(roi, x_shape, ph, pw, scale, sampling_ratio, device):
+    """(image, Wy [PH, H], Wx [PW, W], samples per bin) or None: the bilinear weights are separable."""
+    N, H, W, _ = x_shape
+    c = _roi_coords(roi, N, scale)
+    if c is None:
+        return None
+    n, x1, y1, x2, y2 = c
+    rw, rh = max(x2 - x1, np.float32(1)), max(y2 - y1, np.float32(1))
+    bh, bw = rh / np.float32(ph), rw / np.float32(pw)
+    gh = sampling_ratio if sampling_ratio > 0 else int(math.ceil(rh / np.float32(ph)))
+    gw = sampling_ratio if sampling_ratio > 0 else int(math.ceil(rw / np.float32(pw)))
+    gh, gw = min(gh, ROI_ALIGN_MAX_GRID), min(gw, ROI_ALIGN_MAX_GRID)
+    wy, wx = _roi_align_axis(y1, bh, ph, gh, H), _roi_align_axis(x1, bw, pw, gw, W)
+    return n, torch.from_numpy(wy).to(device), torch.from_numpy(wx).to(device), gh * gw
+
+
+def roi_align_forward(x, rois, ph, pw, scale, sampling_ratio=0):
+    """ROIAlign (aligned = false): the mean of ``sampling_ratio`` (0: ceil(roi / pooled)) squared bilinear
+    samples per bin; coordinates scaled and not rounded, the ROI at least one pixel wide and high."""
+    table = rois.detach().float().cpu().numpy()
+    y = torch.zeros((len(table), ph, pw, x.shape[3]), dtype=torch.float32, device=x.device)
+    for r, roi in enumerate(table):
+        wts = _roi_align_weights(roi, x.shape, ph, pw, scale, sampling_ratio, x.device)
+        if wts is not None:
+            n, wy, wx, count = wts
+            y[r] = torch.einsum("ph,hwc,qw->pqc", wy, x[n].float(), wx) / count
+    return y.to(x.dtype)
+
+
+def roi_align_backward(dy, rois, x_shape, ph, pw, scale, sampling_ratio=0):
+    """Gradient of roi_align_forward to x."""
+    table = rois.detach().float().cpu().numpy()
+    dx = torch.zeros(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    for r, roi in enumerate(table):
+        wts = _roi_align_weights(roi, x_shape, ph, pw, scale, sampling_ratio, dy.device)
+        if wts is not None:
+            n, wy, wx, count = wts
+            dx[n] += torch.einsum("ph,pqc,qw->hwc", wy, dy[r].float(), wx) / count
+    return dx.to(dy.dtype)
+
+
+def _smooth_l1_diff(pred, target, in_w):
+    d = pred.float() - target.float().reshape(pred.shape)
+    return d if in_w is None else d * in_w.float().reshape(pred.shape)
+
+
+def smooth_l1_forward(pred, target, in_w=None, out_w=None, sigma=1.0):
+    """SmoothL1Loss (smooth_L1_loss_layer.cu of the Fast R-CNN fork): d = in_w (pred - target), f(d) = 0.5
+    sigma^2 d^2 below 1 / sigma^2, else |d| - 0.5 / sigma^2; sum(out_w f) / pred.shape[0] as a 0-d fp32."""
+    d, s2 = _smooth_l1_diff(pred, target, in_w), float(sigma) ** 2
+    f = torch.where(d.abs() < 1.0 / s2, 0.5 * s2 * d * d, d.abs() - 0.5 / s2)
+    if out_w is not None:
+        f = f * out_w.float().reshape(pred.shape)
+    return (f.sum() / pred.shape[0]).reshape(())
+
+
+def smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_target=False):
+    """(gradient to pred in its dtype, gradient to target in fp32 or None): loss_weight / num in_w out_w f'(d)
+    and its negative."""
+    d, s2 = _smooth_l1_diff(pred, target, in_w), float(sigma) ** 2
+    g = torch.where(d.abs() < 1.0 / s2, s2 * d, torch.sign(d)) * (loss_weight.float() / pred.shape[0])
+    for wgt in (in_w, out_w):
+        if wgt is not None:
+            g = g * wgt.float().reshape(pred.shape)
+    return g.to(pred.dtype), (-g).reshape(target.shape) if need_target else None
 
 
 def relu_forward(x, slope=0.0):

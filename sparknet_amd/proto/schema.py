@@ -117,6 +117,10 @@ MESSAGES: dict[str, tuple[dict, list]] = {
         o("python_param", 130, "PythonParameter"), o("reduction_param", 136, "ReductionParameter"),
         o("relu_param", 123, "ReLUParameter"), o("reshape_param", 133, "ReshapeParameter"),
         o("shuffle_channel_param", 164, "ShuffleChannelParameter"),  # this project's own field number
+        o("roi_align_param", 165, "ROIAlignParameter"),  # this project's own field number
+        # the py-faster-rcnn fork's numbers as remembered; the fork could not be consulted (docs/COMPONENTS.md)
+        o("roi_pooling_param", 8266711, "ROIPoolingParameter"),
+        o("smooth_l1_loss_param", 8266712, "SmoothL1LossParameter"),
         o("sigmoid_param", 124, "SigmoidParameter"), o("softmax_param", 125, "SoftmaxParameter"),
         o("spp_param", 132, "SPPParameter"), o("slice_param", 126, "SliceParameter"),
         o("tanh_param", 127, "TanHParameter"), o("threshold_param", 128, "ThresholdParameter"),
@@ -203,6 +207,11 @@ MESSAGES: dict[str, tuple[dict, list]] = {
     "ReLUParameter": ({"Engine": ENGINE}, [o("negative_slope", 1, "float", 0),
                                            o("engine", 2, "ReLUParameter.Engine", "DEFAULT")]),
     "CropParameter": ({}, [o("axis", 1, "int32", 2), r("offset", 2, "uint32")]),
+    "ROIPoolingParameter": ({}, [o("pooled_h", 1, "uint32", 0), o("pooled_w", 2, "uint32", 0),
+                                 o("spatial_scale", 3, "float", 1)]),
+    "ROIAlignParameter": ({}, [o("pooled_h", 1, "uint32", 0), o("pooled_w", 2, "uint32", 0),
+                               o("spatial_scale", 3, "float", 1), o("sampling_ratio", 4, "uint32", 0)]),
+    "SmoothL1LossParameter": ({}, [o("sigma", 1, "float", 1)]),
     "ReshapeParameter": ({}, [o("shape", 1, "BlobShape"), o("axis", 2, "int32", 0), o("num_axes", 3, "int32", -1)]),
     "SigmoidParameter": ({"Engine": ENGINE}, [o("engine", 1, "SigmoidParameter.Engine", "DEFAULT")]),
     "SliceParameter": ({}, [o("axis", 3, "int32", 1), r("slice_point", 2, "uint32"), o("slice_dim", 1, "uint32", 1)]),
