@@ -48,10 +48,12 @@ HIP_FLAGS = [
 # epilogue from bringing them in unnoticed.  conv_wgroup.hip, conv_xdw.hip, conv_gpw.hip and conv_updw.hip follow it.  The older
 # files are built as they always were.  roi.hip also turns contraction off: its bin edges and sample
 # positions are defined by their fp32 order of operations, so no product may fuse into a following sum.
+# proposal.hip follows roi.hip: the decoded boxes and the IoUs that decide the NMS are defined the same way.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_TU_FLAGS = {"conv_tstride.hip": _NO_PACKED_FP32, "conv_wgroup.hip": _NO_PACKED_FP32,
                 "conv_xdw.hip": _NO_PACKED_FP32, "conv_gpw.hip": _NO_PACKED_FP32,
-                "conv_updw.hip": _NO_PACKED_FP32, "roi.hip": _NO_PACKED_FP32 + ["-ffp-contract=off"]}
+                "conv_updw.hip": _NO_PACKED_FP32, "roi.hip": _NO_PACKED_FP32 + ["-ffp-contract=off"],
+                "proposal.hip": _NO_PACKED_FP32 + ["-ffp-contract=off"]}
 # host C++ runtime: g++ against the HIP runtime API (hipHostMalloc / hipMemcpyAsync /
 # events); the HIP platform macro selects the AMD backend of the runtime headers.
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-pthread", "-Wall", f"-I{CSRC / 'runtime'}",

@@ -207,6 +207,9 @@ def create_layer(lp, ctx) -> Layer:
     """LayerRegistry::CreateLayer (layer_factory.hpp:74-83)."""
     from .. import layers  # noqa: F401  (populates the registry)
     t = lp.type
+    pp = lp.python_param
+    if t == "Python" and (pp.module, pp.layer) == ("rpn.proposal_layer", "ProposalLayer"):
+        t = "Proposal"  # the public Faster R-CNN test nets load unchanged: layers.vision.ProposalLayer reads param_str
     if t not in _REGISTRY:
         raise KeyError(f"Unknown layer type: {t!r} (known: {', '.join(sorted(_REGISTRY))})")
     return _REGISTRY[t](lp, ctx)

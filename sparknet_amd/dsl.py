@@ -146,10 +146,14 @@ def ReLULayer(name, bottom, *, top=None, in_place=False):
     return lp
 
 
-def SoftmaxWithLoss(name, bottom, *, loss_weight=None, top=None):
+def SoftmaxWithLoss(name, bottom, *, loss_weight=None, top=None, ignore_label=None, normalize=None):
     lp = _base("SoftmaxWithLoss", name, bottom, top)
     lp.loss_param.SetInParent()
     lp.softmax_param.SetInParent()
+    if ignore_label is not None:
+        lp.loss_param.ignore_label = ignore_label
+    if normalize is not None:
+        lp.loss_param.normalize = normalize
     if loss_weight is not None:
         lp.loss_weight.append(loss_weight)
     return lp
@@ -289,6 +293,33 @@ def SmoothL1LossLayer(name, bottom, sigma=1.0, *, loss_weight=None, top=None):
     return lp
 
 
+def ProposalLayer(name, bottom, *, feat_stride=16, base_size=16, min_size=16, ratios=(0.5, 1, 2), scales=(8, 16, 32),
+                  pre_nms_topn=6000, post_nms_topn=300, nms_thresh=0.7, top=None):
+    """The RPN's proposal layer of ``bottom = [scores, deltas, im_info]``; ``top``: ``[rois]`` or ``[rois, scores]``."""
+    lp = _base("Proposal", name, bottom, top)
+    p = lp.proposal_param
+    p.feat_stride, p.base_size, p.min_size = feat_stride, base_size, min_size
+    p.ratio.extend(ratios)
+    p.scale.extend(scales)
+    p.pre_nms_topn, p.post_nms_topn, p.nms_thresh = pre_nms_topn, post_nms_topn, nms_thresh
+    return lp
+
+
+def ReshapeLayer(name, bottom, shape, *, top=None):
+    """``shape``: Caffe's reshape dims (0 copies the bottom's, -1 is inferred)."""
+    lp = _base("Reshape", name, bottom, top)
+    lp.reshape_param.shape.dim.extend(shape)
+    return lp
+
+
+def SoftmaxLayer(name, bottom, axis=1, *, top=None):
+    lp = _base("Softmax", name, bottom, top)
+    lp.softmax_param.SetInParent()
+    if axis != 1:
+        lp.softmax_param.axis = axis
+    return lp
+
+
 def SigmoidLayer(name, bottom, *, top=None, in_place=False):
     return _base("Sigmoid", name, bottom, list(bottom) if in_place else top)
 
@@ -359,5 +390,8 @@ crop_layer = CropLayer
 roi_pooling_layer = ROIPoolingLayer
 roi_align_layer = ROIAlignLayer
 smooth_l1_loss_layer = SmoothL1LossLayer
+proposal_layer = ProposalLayer
+reshape_layer = ReshapeLayer
+softmax_layer = SoftmaxLayer
 sigmoid_layer = SigmoidLayer
 net_param = NetParam

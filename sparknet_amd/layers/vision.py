@@ -987,5 +987,76 @@ class ROIAlignLayer(_ROILayer):
                                             self.scale, self.sampling).to(b.dtype)
 
 
+@register("Proposal")
+class ProposalLayer(Layer):
+    """The proposal layer of Faster R-CNN's region-proposal network (rpn/proposal_layer.py of the public code).
+    Bottoms ``[scores [N, 2A, H, W], deltas [N, 4A, H, W], im_info [N, 3]]`` with the foreground scores in
+    channels A .. 2A-1, anchor a's (dx, dy, dw, dh) in channels 4a .. 4a+3 and im_info rows (height, width,
+    scale); tops ``rois [N post_nms_topn, 5]`` as (image, x1, y1, x2, y2) and optionally ``scores [N
+    post_nms_topn, 1]``, both fp32.  Per image the A H W anchors are decoded, clipped, filtered by ``min_size``
+    scale, ranked by score (the lower index first among equals), cut to ``pre_nms_topn`` (0: all), thinned by
+    greedy NMS at IoU > ``nms_thresh`` and cut to ``post_nms_topn``; an image's unused rows are (-1, 0, 0, 0, 0)
+    with score 0, which the ROI layers ignore.  ``count`` holds the survivors per image as a device int32 tensor
+    that the layer never reads.  No gradient.  bf16 GPU nets: four launches of csrc/kernels/proposal.hip,
+    capturable; elsewhere ops.ref.  The layer is also built from the public ``Python`` layer of module
+    ``rpn.proposal_layer``, whose param_str gives ``feat_stride`` and ``scales`` and whose remaining values are
+    the public config's for the phase."""
+    exact_bottoms = 3
+    min_tops = 1
+    max_tops = 2
+
+    def layer_setup(self, bottoms, tops):
+        if self.lp.type == "Python":
+            import ast
+            given = ast.literal_eval("{" + self.lp.python_param.param_str + "}")
+            unknown = set(given) - {"feat_stride", "scales"}
+            if unknown:
+                raise ValueError(f"Proposal {self.name!r}: param_str keys {sorted(unknown)} are not known")
+            train = self.phase == proto.TRAIN
+            self.feat_stride, scales = int(given.get("feat_stride", 16)), given.get("scales", (8, 16, 32))
+            base, ratios, self.min_size, self.nms_thresh = 16, (0.5, 1, 2), 16.0, 0.7
+            self.pre, self.post = (12000, 2000) if train else (6000, 300)
+        else:
+            p = self.lp.proposal_param
+            self.feat_stride, base, self.min_size = int(p.feat_stride), int(p.base_size), float(p.min_size)
+            ratios, scales = tuple(p.ratio) or (0.5, 1, 2), tuple(p.scale) or (8, 16, 32)
+            self.pre, self.post, self.nms_thresh = int(p.pre_nms_topn), int(p.post_nms_topn), float(p.nms_thresh)
+        if (self.feat_stride < 1 or base < 1 or not self.min_size >= 0 or min(ratios) <= 0 or min(scales) <= 0
+                or self.post < 1 or (self.pre and self.post > self.pre) or not 0 <= self.nms_thresh <= 1):
+            raise ValueError(f"Proposal {self.name!r}: feat_stride = {self.feat_stride}, base_size = {base}, ratios "
+                             f"{ratios} and scales {scales} must be positive, min_size = {self.min_size} not "
+                             f"negative, 1 <= post_nms_topn = {self.post} <= pre_nms_topn = {self.pre} (or 0: all) "
+                             f"and nms_thresh = {self.nms_thresh} in [0, 1]")
+        self.anchors = torch.from_numpy(ops.ref.proposal_anchors(base, ratios, scales)).to(self.device)
+        self.count = None
+
+    def reshape(self, bottoms, tops):
+        s, d, info = bottoms
+        A = self.anchors.shape[0]
+        if (len(s.shape) != 4 or len(d.shape) != 4 or s.shape[1] != 2 * A or d.shape[1] != 4 * A
+                or (s.shape[0], *s.shape[2:]) != (d.shape[0], *d.shape[2:]) or tuple(info.shape) != (s.shape[0], 3)):
+            raise ValueError(f"Proposal {self.name!r}: bottoms of shape [N, {2 * A}, H, W], [N, {4 * A}, H, W] and "
+                             f"[N, 3] are needed, got {tuple(s.shape)}, {tuple(d.shape)} and {tuple(info.shape)}")
+        if any(t is b for t in tops for b in bottoms):
+            raise ValueError(f"Proposal {self.name!r} cannot run in place")
+        tops[0].reshape((s.shape[0] * self.post, 5), torch.float32)
+        if len(tops) > 1:
+            tops[1].reshape((s.shape[0] * self.post, 1), torch.float32)
+
+    def forward(self, bottoms, tops):
+        rois, scores, self.count = ops.proposal(bottoms[0].data, bottoms[1].data, bottoms[2].data.float(), self.anchors,
+                                                self.feat_stride, self.min_size, self.pre, self.post, self.nms_thresh)
+        tops[0].data = rois
+        if len(tops) > 1:
+            tops[1].data = scores
+
+    def backward(self, tops, propagate_down, bottoms):
+        if any(propagate_down):
+            raise ValueError(f"Proposal {self.name!r} cannot backpropagate to its bottoms")
+
+    def allow_force_backward(self, bottom_id: int) -> bool:
+        return False
+
+
 __all__ = ["ConvolutionLayer", "DeconvolutionLayer", "PoolingLayer", "LRNLayer", "InnerProductLayer",
-           "Im2colLayer", "ROIPoolingLayer", "ROIAlignLayer", "POOL_MAX", "POOL_AVE"]
+           "Im2colLayer", "ROIPoolingLayer", "ROIAlignLayer", "ProposalLayer", "POOL_MAX", "POOL_AVE"]

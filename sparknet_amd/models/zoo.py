@@ -22,6 +22,8 @@
   three depthwise Deconvolution upsamplings fused with cropped pool4 / pool3 scores
 * ``fast_rcnn``      — not in the reference; Fast R-CNN (Girshick 2015) on the CaffeNet or VGG-16 trunk: ROIPooling
   (or ROIAlign) of conv5 over given ROIs, fc6 / fc7, a SoftmaxWithLoss and a SmoothL1Loss head
+* ``faster_rcnn``    — not in the reference; Faster R-CNN (Ren et al. 2015): the same trunks under a region-proposal
+  network; TRAIN is the stage-1 RPN net, TEST runs the Proposal layer (decode, top-k, NMS) into ROIPooling and the head
 * ``se_resnet50``    — not in the reference; SE-ResNet-50 (Hu et al. 2018): ResNet-50 with a squeeze-and-
   excitation tail per block (global pool, two 1x1 convolutions, Sigmoid) gating the block output in an Axpy
 
@@ -35,7 +37,7 @@ from .. import proto
 from ..dsl import (AccuracyLayer, AxpyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer,
                    Include, InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer,
                    ScaleLayer, ShuffleChannelLayer, SigmoidLayer, SoftmaxWithLoss, CropLayer, DeconvolutionLayer,
-                   ROIAlignLayer, ROIPoolingLayer, SmoothL1LossLayer)
+                   ROIAlignLayer, ROIPoolingLayer, SmoothL1LossLayer, ProposalLayer, ReshapeLayer, SoftmaxLayer)
 from ..ops.spec import PoolSpec
 
 WB = [(1.0, 1.0), (2.0, 0.0)]   # weight / bias lr & decay mults used by the ImageNet models
@@ -307,6 +309,37 @@ def fcn8s(classes=21, train_batch=1, test_batch=1, crop=500, width=1.0):
     return NetParam("voc-fcn8s", *L)
 
 
+def _rcnn_trunk(who, trunk, ch, size):
+    """The detection nets' trunk from ``data`` to ``conv5`` (CaffeNet) / ``conv5_3`` (VGG-16) without its last pool,
+    its first layers frozen as published: (layers, top blob, ROI bins, the top's height = width for a ``size``
+    square input)."""
+    if trunk not in ("caffenet", "vgg16"):
+        raise ValueError(f"{who}: trunk {trunk!r} is neither 'caffenet' nor 'vgg16'")
+    frozen = [(0.0, 0.0), (0.0, 0.0)]
+    half = lambda n, k: -(-(n - k) // 2) + 1  # a stride-2 pooling with Caffe's ceil
+    L = []
+    if trunk == "caffenet":
+        L += [_conv("conv1", "data", 11, ch(96), stride=4, wf=_g(0.01), bf=_c(0.0), param=frozen),
+              _relu("relu1", "conv1"), _pool("pool1", "conv1", 3, 2), LRNLayer("norm1", ["pool1"], 5, 1e-4, 0.75),
+              _conv("conv2", "norm1", 5, ch(256), pad=2, group=2, wf=_g(0.01), bf=_c(1.0)),
+              _relu("relu2", "conv2"), _pool("pool2", "conv2", 3, 2), LRNLayer("norm2", ["pool2"], 5, 1e-4, 0.75),
+              _conv("conv3", "norm2", 3, ch(384), pad=1, wf=_g(0.01), bf=_c(0.0)), _relu("relu3", "conv3"),
+              _conv("conv4", "conv3", 3, ch(384), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu4", "conv4"),
+              _conv("conv5", "conv4", 3, ch(256), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu5", "conv5")]
+        return L, "conv5", (6, 6), half(half((size - 11) // 4 + 1, 3), 3)
+    x, side = "data", size
+    for stage, (n, reps) in enumerate([(64, 2), (128, 2), (256, 3), (512, 3), (512, 3)], 1):
+        for r in range(1, reps + 1):
+            name = f"conv{stage}_{r}"
+            L += [_conv(name, x, 3, ch(n), pad=1, wf=MSRA, bf=_c(0.0), param=frozen if stage <= 2 else WB),
+                  _relu(f"relu{stage}_{r}", name)]
+            x = name
+        if stage < 5:
+            L.append(_pool(f"pool{stage}", x, 2, 2))
+            x, side = f"pool{stage}", half(side, 2)
+    return L, x, (7, 7), side
+
+
 def fast_rcnn(trunk="caffenet", classes=21, images=2, rois=128, size=600, align=False, width=1.0):
     """Fast R-CNN (Girshick 2015; layer and blob names of the public CaffeNet / VGG16 train nets): not in the
     reference.  Inputs ``data`` [images, 3, size, size], ``rois`` [rois, 5] as (image, x1, y1, x2, y2),
@@ -316,33 +349,11 @@ def fast_rcnn(trunk="caffenet", classes=21, images=2, rois=128, size=600, align=
     (7 x 7 for VGG-16) bins at scale 1 / 16 (csrc/kernels/roi.hip); ``fc6`` / ``fc7`` with dropout feed
     ``cls_score`` into ``loss_cls`` (SoftmaxWithLoss) and ``bbox_pred`` into ``loss_bbox`` (SmoothL1Loss).
     ``width`` scales the trunk's and the fc layers' channel counts (rounded to multiples of 8)."""
-    if trunk not in ("caffenet", "vgg16"):
-        raise ValueError(f"fast_rcnn: trunk {trunk!r} is neither 'caffenet' nor 'vgg16'")
     ch = lambda n: max(8, int(n * width / 8 + 0.5) * 8)
-    frozen = [(0.0, 0.0), (0.0, 0.0)]
     L = [RDDLayer("data", [images, 3, size, size]), RDDLayer("rois", [rois, 5]), RDDLayer("labels", [rois])]
     L += [RDDLayer(n, [rois, 4 * classes]) for n in ("bbox_targets", "bbox_inside_weights", "bbox_outside_weights")]
-    if trunk == "caffenet":
-        L += [_conv("conv1", "data", 11, ch(96), stride=4, wf=_g(0.01), bf=_c(0.0), param=frozen),
-              _relu("relu1", "conv1"), _pool("pool1", "conv1", 3, 2), LRNLayer("norm1", ["pool1"], 5, 1e-4, 0.75),
-              _conv("conv2", "norm1", 5, ch(256), pad=2, group=2, wf=_g(0.01), bf=_c(1.0)),
-              _relu("relu2", "conv2"), _pool("pool2", "conv2", 3, 2), LRNLayer("norm2", ["pool2"], 5, 1e-4, 0.75),
-              _conv("conv3", "norm2", 3, ch(384), pad=1, wf=_g(0.01), bf=_c(0.0)), _relu("relu3", "conv3"),
-              _conv("conv4", "conv3", 3, ch(384), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu4", "conv4"),
-              _conv("conv5", "conv4", 3, ch(256), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu5", "conv5")]
-        x, pooled = "conv5", (6, 6)
-    else:
-        x = "data"
-        for stage, (n, reps) in enumerate([(64, 2), (128, 2), (256, 3), (512, 3), (512, 3)], 1):
-            for r in range(1, reps + 1):
-                name = f"conv{stage}_{r}"
-                L += [_conv(name, x, 3, ch(n), pad=1, wf=MSRA, bf=_c(0.0), param=frozen if stage <= 2 else WB),
-                      _relu(f"relu{stage}_{r}", name)]
-                x = name
-            if stage < 5:
-                L.append(_pool(f"pool{stage}", x, 2, 2))
-                x = f"pool{stage}"
-        pooled = (7, 7)
+    trunk_layers, x, pooled, _ = _rcnn_trunk("fast_rcnn", trunk, ch, size)
+    L += trunk_layers
     L.append(ROIAlignLayer("roi_pool5", [x, "rois"], pooled, 1.0 / 16, 2) if align else
              ROIPoolingLayer("roi_pool5", [x, "rois"], pooled, 1.0 / 16))
     L += [_ip("fc6", "roi_pool5", ch(4096), _g(0.005), _c(0.1)), _relu("relu6", "fc6"), DropoutLayer("drop6", ["fc6"], 0.5),
@@ -351,6 +362,52 @@ def fast_rcnn(trunk="caffenet", classes=21, images=2, rois=128, size=600, align=
           SoftmaxWithLoss("loss_cls", ["cls_score", "labels"], loss_weight=1.0),
           SmoothL1LossLayer("loss_bbox", ["bbox_pred", "bbox_targets", "bbox_inside_weights", "bbox_outside_weights"],
                             loss_weight=1.0)]
+    return NetParam("CaffeNet" if trunk == "caffenet" else "VGG_ILSVRC_16_layers", *L)
+
+
+def _only(include, *layers):
+    for lp in layers:
+        lp.include.add().phase = proto.TRAIN if include is Include.Train else proto.TEST
+    return list(layers)
+
+
+def faster_rcnn(trunk="vgg16", classes=21, images=1, size=600, width=1.0, pre_nms_topn=6000, post_nms_topn=300,
+                nms_thresh=0.7):
+    """Faster R-CNN (Ren et al. 2015; layer and blob names of the public alternating-optimisation nets): not in
+    the reference.  Inputs ``data`` [images, 3, size, size] and ``im_info`` [images, 3] = (height, width, scale).
+    ``fast_rcnn``'s trunk feeds the region-proposal network: ``rpn_conv/3x3``, ``rpn_cls_score`` (18) and
+    ``rpn_bbox_pred`` (36) for 9 anchors per conv5 pixel.  TRAIN is the stage-1 RPN training net with the anchor
+    targets as inputs (``rpn_labels`` [images, 1, 9 H, W], ``rpn_bbox_targets`` and its inside / outside weights
+    [images, 36, H, W]), ``rpn_loss_cls`` and ``rpn_loss_bbox``.  TEST is the detector: ``proposal``
+    (csrc/kernels/proposal.hip) turns the RPN's outputs into ``images post_nms_topn`` ROIs, unused rows carrying
+    image -1, for ``roi_pool5`` and the Fast R-CNN head.  ``width`` scales the channel counts."""
+    ch = lambda n: max(8, int(n * width / 8 + 0.5) * 8)
+    L, x, pooled, side = _rcnn_trunk("faster_rcnn", trunk, ch, size)
+    L = [RDDLayer("data", [images, 3, size, size]), RDDLayer("im_info", [images, 3])] + L
+    L += _only(Include.Train, RDDLayer("rpn_labels", [images, 1, 9 * side, side]),
+               *[RDDLayer(n, [images, 36, side, side])
+                 for n in ("rpn_bbox_targets", "rpn_bbox_inside_weights", "rpn_bbox_outside_weights")])
+    L += [_conv("rpn_conv/3x3", x, 3, ch(512), pad=1, wf=_g(0.01), bf=_c(0.0)), _relu("rpn_relu/3x3", "rpn_conv/3x3"),
+          _conv("rpn_cls_score", "rpn_conv/3x3", 1, 18, wf=_g(0.01), bf=_c(0.0)),
+          _conv("rpn_bbox_pred", "rpn_conv/3x3", 1, 36, wf=_g(0.01), bf=_c(0.0)),
+          ReshapeLayer("rpn_cls_score_reshape", ["rpn_cls_score"], [0, 2, -1, 0])]
+    L += _only(Include.Train,
+               SoftmaxWithLoss("rpn_loss_cls", ["rpn_cls_score_reshape", "rpn_labels"], loss_weight=1.0,
+                               ignore_label=-1, normalize=True, top=["rpn_cls_loss"]),
+               SmoothL1LossLayer("rpn_loss_bbox", ["rpn_bbox_pred", "rpn_bbox_targets", "rpn_bbox_inside_weights",
+                                                   "rpn_bbox_outside_weights"], sigma=3.0, loss_weight=1.0,
+                                 top=["rpn_loss_bbox"]))
+    L += _only(Include.Test,
+               SoftmaxLayer("rpn_cls_prob", ["rpn_cls_score_reshape"]),
+               ReshapeLayer("rpn_cls_prob_reshape", ["rpn_cls_prob"], [0, 18, -1, 0]),
+               ProposalLayer("proposal", ["rpn_cls_prob_reshape", "rpn_bbox_pred", "im_info"], top=["rois"],
+                             pre_nms_topn=pre_nms_topn, post_nms_topn=post_nms_topn, nms_thresh=nms_thresh),
+               ROIPoolingLayer("roi_pool5", [x, "rois"], pooled, 1.0 / 16),
+               _ip("fc6", "roi_pool5", ch(4096), _g(0.005), _c(0.1)), _relu("relu6", "fc6"),
+               DropoutLayer("drop6", ["fc6"], 0.5),
+               _ip("fc7", "fc6", ch(4096), _g(0.005), _c(0.1)), _relu("relu7", "fc7"), DropoutLayer("drop7", ["fc7"], 0.5),
+               _ip("cls_score", "fc7", classes, _g(0.01), _c(0.0)), _ip("bbox_pred", "fc7", 4 * classes, _g(0.001), _c(0.0)),
+               SoftmaxLayer("cls_prob", ["cls_score"]))
     return NetParam("CaffeNet" if trunk == "caffenet" else "VGG_ILSVRC_16_layers", *L)
 
 
@@ -730,6 +787,11 @@ def fast_rcnn_solver(net=None):  # the public Fast R-CNN solvers
                    average_loss=100, max_iter=40000, momentum=0.9, weight_decay=5e-4)
 
 
+def faster_rcnn_solver(net=None):  # the public stage-1 RPN solver of the alternating optimisation
+    return _solver(net or faster_rcnn(), base_lr=0.001, lr_policy="step", gamma=0.1, stepsize=60000, display=20,
+                   average_loss=100, max_iter=80000, momentum=0.9, weight_decay=5e-4)
+
+
 def resnext50_solver(net=None):  # ResNet-50's schedule
     return _solver(net or resnext50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
                    gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
@@ -749,6 +811,7 @@ MODELS = {
     "resnext50": (resnext50, resnext50_solver), "se_resnet50": (se_resnet50, se_resnet50_solver),
     "mnasnet": (mnasnet, mnasnet_solver), "shufflenet": (shufflenet, shufflenet_solver),
     "fcn8s": (fcn8s, fcn8s_solver), "fast_rcnn": (fast_rcnn, fast_rcnn_solver),
+    "faster_rcnn": (faster_rcnn, faster_rcnn_solver),
 }
 
 

@@ -155,6 +155,16 @@ def smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_targe
     return impl.smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_target)
 
 
+def proposal(scores, deltas, im_info, anchors, feat_stride, min_size, pre_nms_topn, post_nms_topn, nms_thresh):
+    """The RPN's proposal layer on the stored layout: (rois [N post, 5], scores [N post, 1], count [N]).  The
+    kernels of csrc/kernels/proposal.hip where hip.proposal_ok accepts the operands; otherwise ops.ref, which
+    reads the boxes on the host (the CPU, the fp32 device mode, other dtypes, larger problems,
+    SN_FEATURES=proposal_kernels=0)."""
+    use = _gpu(scores) and _hipmod().proposal_ok(scores, deltas, im_info, pre_nms_topn, post_nms_topn, nms_thresh)
+    return (_hipmod() if use else ref).proposal(scores, deltas, im_info, anchors, feat_stride, min_size,
+                                                pre_nms_topn, post_nms_topn, nms_thresh)
+
+
 def pool_backward(dy, x, s, aux=None, y=None, gate=False):
     """gate=True: x is a slope-0 in-place ReLU output whose backward is fused here (MAX
     pooling on the GPU encodes it in the forward's argmax mask)."""

@@ -716,6 +716,61 @@ def smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_targe
     return dp, dt
 
 
+PROPOSAL_DECODE, PROPOSAL_SELECT = "proposal_decode", "proposal_select"
+PROPOSAL_MASK, PROPOSAL_SCAN = "proposal_mask", "proposal_scan"
+PROPOSAL_MAX_BOXES = 65535   # boxes of an image: the index is the low half of a 32-bit key
+PROPOSAL_MAX_PRE = 16384     # keys sorted in LDS
+PROPOSAL_MAX_ANCHORS = 1024  # base anchors held in LDS
+
+
+def proposal_ok(scores, deltas, im_info, pre_nms_topn=6000, post_nms_topn=300, nms_thresh=0.7) -> bool:
+    """Operands the proposal kernels take (csrc/kernels/proposal.hip): bf16 4-D NHWC ``scores`` [N, H, W, 2A] and
+    ``deltas`` [N, H, W, 4A], fp32 ``im_info`` [N, 3] on their device, 1 <= A H W <= 65535 boxes of at most 1024
+    anchors per pixel, 1 <= post_nms_topn <= pre_nms_topn <= 16384 (pre_nms_topn 0: every box, served up to 16384
+    boxes), 0 <= nms_thresh <= 1.  The switch is read on every call (SN_FEATURES=proposal_kernels=0)."""
+    if not (scores.dim() == 4 and deltas.dim() == 4 and scores.dtype == BF16 and deltas.dtype == BF16
+            and scores.shape[:3] == deltas.shape[:3] and scores.shape[3] % 2 == 0
+            and deltas.shape[3] == 2 * scores.shape[3] and im_info.dtype == torch.float32
+            and tuple(im_info.shape) == (scores.shape[0], 3) and scores.device == deltas.device == im_info.device):
+        return False
+    N, H, W, A2 = scores.shape
+    boxes = A2 // 2 * H * W
+    if not (1 <= N <= 65535 and 1 <= A2 // 2 <= PROPOSAL_MAX_ANCHORS and 1 <= boxes <= PROPOSAL_MAX_BOXES):
+        return False
+    most = pre_nms_topn if pre_nms_topn > 0 else boxes
+    return (0 <= pre_nms_topn <= PROPOSAL_MAX_PRE and 1 <= post_nms_topn <= most <= PROPOSAL_MAX_PRE
+            and 0 <= nms_thresh <= 1 and features.enabled("proposal_kernels"))
+
+
+def proposal(scores, deltas, im_info, anchors, feat_stride, min_size, pre_nms_topn, post_nms_topn, nms_thresh):
+    """The proposal layer in four launches, nothing read on the host: (rois [N post, 5] fp32 as (image, x1, y1,
+    x2, y2), scores [N post, 1] fp32, count [N] int32).  ``anchors``: the fp32 [A, 4] base anchors on the device."""
+    scores, deltas, im_info, anchors = _c(scores), _c(deltas), _c(im_info), _c(anchors)
+    if not proposal_ok(scores, deltas, im_info, pre_nms_topn, post_nms_topn, nms_thresh):
+        raise ValueError(f"proposal: scores {tuple(scores.shape)} {scores.dtype} / deltas {tuple(deltas.shape)} "
+                         f"{deltas.dtype} / im_info {tuple(im_info.shape)} {im_info.dtype}, pre_nms_topn "
+                         f"{pre_nms_topn}, post_nms_topn {post_nms_topn}, nms_thresh {nms_thresh} are not served "
+                         f"by the proposal kernels")
+    N, H, W, A = *scores.shape[:3], scores.shape[3] // 2
+    if tuple(anchors.shape) != (A, 4) or anchors.dtype != torch.float32 or anchors.device != scores.device:
+        raise ValueError(f"proposal: anchors {tuple(anchors.shape)} {anchors.dtype} for {A} anchors per pixel")
+    if not (1 <= feat_stride <= 65535 and min_size >= 0):
+        raise ValueError(f"proposal: feat_stride {feat_stride}, min_size {min_size}")
+    B, pre, post, dev = A * H * W, int(pre_nms_topn), int(post_nms_topn), scores.device
+    K = min(pre, B) if pre > 0 else B
+    nbk = -(-K // 64)
+    new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+    boxes, keys = new((N, B, 4)), new((N, B), torch.int32)
+    sboxes, sscores, cnt = new((N, K, 4)), new((N, K)), new((N,), torch.int32)
+    mask = new((N, nbk * 64, nbk), torch.int64)
+    rois, out, count = new((N * post, 5)), new((N * post, 1)), new((N,), torch.int32)
+    call(PROPOSAL_DECODE, scores, deltas, im_info, anchors, boxes, keys, N, H, W, A, int(feat_stride), float(min_size))
+    call(PROPOSAL_SELECT, keys, boxes, sboxes, sscores, cnt, N, B, pre)
+    call(PROPOSAL_MASK, sboxes, cnt, mask, N, B, pre, float(nms_thresh))
+    call(PROPOSAL_SCAN, sboxes, sscores, cnt, mask, rois, out, count, N, B, pre, post, float(nms_thresh))
+    return rois, out, count
+
+
 PATCH_DGRAD = "conv_patch_dgrad"
 PATCH_MIN_ROWS,PATCH_MAX_COLS = 8, 32  # a 256-pixel band of at most 32 columns has at least 8 rows
 

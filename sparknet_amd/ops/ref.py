@@ -419,6 +419,90 @@ def smooth_l1_backward(pred, target, in_w, out_w, sigma, loss_weight, need_targe
     return g.to(pred.dtype), (-g).reshape(target.shape) if need_target else None
 
 
+# --- proposal layer (rpn/proposal_layer.py, generate_anchors.py, nms of the public Faster R-CNN code) --------
+
+def proposal_anchors(base_size=16, ratios=(0.5, 1, 2), scales=(8, 16, 32)):
+    """The public generate_anchors: [len(ratios) len(scales), 4] float32 base anchors (x1, y1, x2, y2) around a
+    ``base_size`` square at the origin, ratios outermost, with numpy's roundings."""
+    ratios, scales = np.asarray(ratios, dtype=np.float64), np.asarray(scales, dtype=np.float64)
+
+    def centred(ws, hs, cx, cy):
+        return np.stack([cx - 0.5 * (ws - 1), cy - 0.5 * (hs - 1), cx + 0.5 * (ws - 1), cy + 0.5 * (hs - 1)], 1)
+
+    centre = 0.5 * (base_size - 1)
+    ws = np.round(np.sqrt(base_size * base_size / ratios))
+    hs = np.round(ws * ratios)
+    out = []
+    for x1, y1, x2, y2 in centred(ws, hs, centre, centre):
+        w, h = x2 - x1 + 1, y2 - y1 + 1
+        out.append(centred(w * scales, h * scales, x1 + 0.5 * (w - 1), y1 + 0.5 * (h - 1)))
+    return np.concatenate(out).astype(np.float32)
+
+
+def _proposal_axis(lo, hi, d, dl):
+    e = hi - lo + 1
+    c = lo + 0.5 * e
+    pc, pe = d * e + c, torch.exp(dl) * e
+    return pc - 0.5 * pe, pc + 0.5 * pe
+
+
+def proposal(scores, deltas, im_info, anchors, feat_stride, min_size, pre_nms_topn, post_nms_topn, nms_thresh):
+    """The proposal layer of Faster R-CNN's RPN on the stored layout, the semantics of csrc/kernels/proposal.hip
+    in fp32: ``scores`` [N, H, W, 2A] (foreground: channels A ..), ``deltas`` [N, H, W, 4A], ``im_info`` [N, 3] =
+    (height, width, scale), ``anchors`` [A, 4]; box ``i = (h W + w) A + a``.  Decode, clip, drop boxes below
+    ``min_size`` scale (and NaN scores, non-finite boxes, images whose im_info is NaN or not positive), rank by
+    score with the lower index first among equals, keep ``pre_nms_topn`` (0: all), greedy NMS at IoU >
+    ``nms_thresh``.  Returns (rois [N post, 5] fp32 as (image, x1, y1, x2, y2), scores [N post, 1] fp32, count
+    [N] int32); an image's unused rows are (-1, 0, 0, 0, 0) with score 0.  The boxes are read on the host for
+    the NMS loop, so this route cannot be captured into a graph."""
+    N, H, W, A2 = scores.shape
+    A, dev, f32 = A2 // 2, scores.device, torch.float32
+    sc = scores[..., A:].float().reshape(N, -1) + 0.0  # -0 ranks, and is reported, as +0
+    d = deltas.float().reshape(N, -1, 4)
+    ws = torch.arange(W, dtype=f32, device=dev) * feat_stride
+    hs = torch.arange(H, dtype=f32, device=dev) * feat_stride
+    shift = torch.stack([ws.expand(H, W), hs[:, None].expand(H, W)] * 2, -1)
+    anc = (torch.as_tensor(anchors, dtype=f32, device=dev) + shift[:, :, None, :]).reshape(-1, 4)
+    info = im_info.float()
+    good = ((info > 0) & torch.isfinite(info)).all(1)
+    x1, x2 = _proposal_axis(anc[:, 0], anc[:, 2], d[..., 0], d[..., 2])
+    y1, y2 = _proposal_axis(anc[:, 1], anc[:, 3], d[..., 1], d[..., 3])
+    raw = torch.stack([x1, y1, x2, y2], -1)
+    top = torch.stack([info[:, 1] - 1, info[:, 0] - 1] * 2, -1)[:, None, :]
+    boxes = torch.maximum(torch.minimum(raw, top), torch.zeros((), dtype=f32, device=dev))
+    lim = (min_size * info[:, 2])[:, None]
+    keep = (torch.isfinite(raw).all(-1) & good[:, None] & ~torch.isnan(sc)
+            & (boxes[..., 2] - boxes[..., 0] + 1 >= lim) & (boxes[..., 3] - boxes[..., 1] + 1 >= lim))
+    rois = torch.zeros((N, post_nms_topn, 5), dtype=f32)
+    rois[..., 0] = -1
+    out_sc = torch.zeros((N, post_nms_topn, 1), dtype=f32)
+    count = torch.zeros(N, dtype=torch.int32)
+    boxes, sc, keep = boxes.cpu(), sc.cpu(), keep.cpu()
+    for n in range(N):
+        idx = torch.nonzero(keep[n]).flatten()
+        order = idx[torch.sort(-sc[n, idx], stable=True).indices]
+        if pre_nms_topn > 0:
+            order = order[:pre_nms_topn]
+        b = boxes[n, order].numpy()
+        area = (b[:, 2] - b[:, 0] + 1) * (b[:, 3] - b[:, 1] + 1)
+        gone, kept = np.zeros(len(b), dtype=bool), []
+        for i in range(len(b)):
+            if gone[i]:
+                continue
+            kept.append(i)
+            if len(kept) == post_nms_topn:
+                break
+            w = np.maximum(np.float32(0), np.minimum(b[i, 2], b[i + 1:, 2]) - np.maximum(b[i, 0], b[i + 1:, 0]) + 1)
+            h = np.maximum(np.float32(0), np.minimum(b[i, 3], b[i + 1:, 3]) - np.maximum(b[i, 1], b[i + 1:, 1]) + 1)
+            inter = w * h
+            gone[i + 1:] |= inter / (area[i] + area[i + 1:] - inter) > np.float32(nms_thresh)
+        k = len(kept)
+        rois[n, :k, 0], rois[n, :k, 1:] = n, torch.from_numpy(b[kept].reshape(k, 4))
+        out_sc[n, :k, 0] = sc[n, order[kept]]
+        count[n] = k
+    return rois.reshape(-1, 5).to(dev), out_sc.reshape(-1, 1).to(dev), count.to(dev)
+
+
 def relu_forward(x, slope=0.0):
     xf = x.float()
     return torch.where(xf > 0, xf, xf * slope).to(x.dtype)

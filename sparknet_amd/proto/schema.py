@@ -118,6 +118,7 @@ MESSAGES: dict[str, tuple[dict, list]] = {
         o("relu_param", 123, "ReLUParameter"), o("reshape_param", 133, "ReshapeParameter"),
         o("shuffle_channel_param", 164, "ShuffleChannelParameter"),  # this project's own field number
         o("roi_align_param", 165, "ROIAlignParameter"),  # this project's own field number
+        o("proposal_param", 166, "ProposalParameter"),  # this project's own field number
         # the py-faster-rcnn fork's numbers as remembered; the fork could not be consulted (docs/COMPONENTS.md)
         o("roi_pooling_param", 8266711, "ROIPoolingParameter"),
         o("smooth_l1_loss_param", 8266712, "SmoothL1LossParameter"),
@@ -212,6 +213,10 @@ MESSAGES: dict[str, tuple[dict, list]] = {
     "ROIAlignParameter": ({}, [o("pooled_h", 1, "uint32", 0), o("pooled_w", 2, "uint32", 0),
                                o("spatial_scale", 3, "float", 1), o("sampling_ratio", 4, "uint32", 0)]),
     "SmoothL1LossParameter": ({}, [o("sigma", 1, "float", 1)]),
+    "ProposalParameter": ({}, [o("feat_stride", 1, "uint32", 16), o("base_size", 2, "uint32", 16),
+                               o("min_size", 3, "float", 16), r("ratio", 4, "float"), r("scale", 5, "float"),
+                               o("pre_nms_topn", 6, "uint32", 6000), o("post_nms_topn", 7, "uint32", 300),
+                               o("nms_thresh", 8, "float", 0.7)]),
     "ReshapeParameter": ({}, [o("shape", 1, "BlobShape"), o("axis", 2, "int32", 0), o("num_axes", 3, "int32", -1)]),
     "SigmoidParameter": ({"Engine": ENGINE}, [o("engine", 1, "SigmoidParameter.Engine", "DEFAULT")]),
     "SliceParameter": ({}, [o("axis", 3, "int32", 1), r("slice_point", 2, "uint32"), o("slice_dim", 1, "uint32", 1)]),
