@@ -52,6 +52,10 @@ def _fill_inputs(net: Net, seed=0):
             R, extent = rois.shape[0], torch.tensor([feat.shape[3], feat.shape[2]]) / layer.scale
             p = (torch.rand(R, 2, 2, generator=g) * extent).sort(dim=1).values
             rois.data.copy_(torch.cat([torch.arange(R).reshape(R, 1) % feat.shape[0], p[:, 0], p[:, 1]], 1))
+        if layer.type_name == "LSTM":  # cont: every stream starts at t = 0 and runs on
+            cont = net.bottom_vecs[li][1]
+            cont.data.fill_(1.0)
+            cont.data[0].zero_()
         if layer.type_name == "Proposal":  # im_info: the data blob's height and width, scale 1
             data = net.blob_by_name("data")
             net.bottom_vecs[li][2].data.copy_(torch.tensor([float(data.shape[2]), float(data.shape[3]), 1.0]))
@@ -87,6 +91,8 @@ def cmd_time(args):
     if args.zoo:
         if args.zoo in ("fast_rcnn", "faster_rcnn"):  # their batch is the image count; --trunk picks the CaffeNet or VGG-16 trunk
             netp = models.build(args.zoo, images=args.batch, trunk=args.trunk)
+        elif args.zoo == "lrcn":  # its batch is the number of streams, 16 frames each
+            netp = models.build(args.zoo, N=args.batch)
         else:
             netp = models.build(args.zoo, train_batch=args.batch, test_batch=args.batch)
     else:

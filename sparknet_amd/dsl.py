@@ -305,6 +305,18 @@ def ProposalLayer(name, bottom, *, feat_stride=16, base_size=16, min_size=16, ra
     return lp
 
 
+def LSTMLayer(name, bottom, numOutput, *, top=None, weight_filler=None, bias_filler=None, param=None):
+    """Upstream's LSTM layer of ``bottom = [x [T, N, ...], cont [T, N]]`` or ``[x, cont, x_static [N, ...]]``."""
+    lp = _base("LSTM", name, bottom, top)
+    lp.recurrent_param.num_output = numOutput
+    if weight_filler is not None:
+        lp.recurrent_param.weight_filler.CopyFrom(_filler(weight_filler))
+    if bias_filler is not None:
+        lp.recurrent_param.bias_filler.CopyFrom(_filler(bias_filler))
+    _params(lp, param)
+    return lp
+
+
 def ReshapeLayer(name, bottom, shape, *, top=None):
     """``shape``: Caffe's reshape dims (0 copies the bottom's, -1 is inferred)."""
     lp = _base("Reshape", name, bottom, top)
@@ -391,6 +403,7 @@ roi_pooling_layer = ROIPoolingLayer
 roi_align_layer = ROIAlignLayer
 smooth_l1_loss_layer = SmoothL1LossLayer
 proposal_layer = ProposalLayer
+lstm_layer = LSTMLayer
 reshape_layer = ReshapeLayer
 softmax_layer = SoftmaxLayer
 sigmoid_layer = SigmoidLayer

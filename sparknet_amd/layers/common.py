@@ -1593,6 +1593,111 @@ class SPPLayer(Layer):
         b.diff = g.to(b.dtype)
 
 
+@register("LSTM")
+class LSTMLayer(Layer):
+    """Upstream BVLC's LSTM layer (lstm_layer.cpp over recurrent_layer.cpp, not in the reference snapshot).
+    Bottoms ``x`` [T, N, ...] (D = the count from axis 2), ``cont`` [T, N] and optionally ``x_static`` [N, ...]; top
+    ``h`` [T, N, H] with H = recurrent_param.num_output.  Blobs in upstream's order: W_xc [4H, D], b_c [4H],
+    W_xc_static [4H, Ds] (with a third bottom only), W_hc [4H, H]; gates i, f, o, g along 4H.  Step t:
+    pre = W_xc x_t + b_c (+ W_xc_static x_static) + W_hc (cont_t h_{t-1}); i, f, o = sigmoid, g = tanh;
+    c_t = cont_t f c_{t-1} + i g; h_t = o tanh(c_t).  A forward starts from the h_T / c_T of the layer's previous
+    forward (zero at construction and after ``reset()``; cont_0 = 0 restarts a stream); the carry is a device
+    copy, so a captured iteration replays it.  No gradient reaches the carried state or ``cont``.  bf16 GPU nets
+    with H % 8 == 0: one launch of csrc/kernels/lstm.hip per timestep and direction around the GEMM engine's
+    products; elsewhere ops.ref.  ``expose_hidden``, ``debug_info`` and the RNN layer are not served."""
+    min_bottoms = 2
+    max_bottoms = 3
+    exact_tops = 1
+    supports_grad_overwrite = True
+
+    def layer_setup(self, bottoms, tops):
+        p = self.lp.recurrent_param
+        if p.expose_hidden:
+            raise ValueError(f"LSTM {self.name!r}: expose_hidden is not served (the state is carried inside the layer)")
+        self.H = int(p.num_output)
+        if self.H < 1:
+            raise ValueError(f"LSTM {self.name!r}: recurrent_param.num_output must be positive")
+        x = bottoms[0]
+        if len(x.shape) < 3:
+            raise ValueError(f"LSTM {self.name!r}: x needs shape [T, N, ...], got {tuple(x.shape)}")
+        self.D = x.count_range(2)
+        wf = p.weight_filler if p.HasField("weight_filler") else None
+        self.w_xc = self.add_param((4 * self.H, self.D), filler=wf)
+        self.b_c = self.add_param((4 * self.H,), filler=p.bias_filler if p.HasField("bias_filler") else None)
+        self.w_xs = self.add_param((4 * self.H, bottoms[2].count_range(1)), filler=wf) if len(bottoms) > 2 else None
+        self.w_hc = self.add_param((4 * self.H, self.H), filler=wf)
+        self.h0 = self.c0 = self.saved = None
+
+    def reshape(self, bottoms, tops):
+        x, cont = bottoms[0], bottoms[1]
+        T, N = x.shape[:2]
+        if x.count_range(2) != self.D or tuple(cont.shape) != (T, N):
+            raise ValueError(f"LSTM {self.name!r}: x [T, N, ...] of {self.D} values per step and cont [T, N] are needed, "
+                             f"got {tuple(x.shape)} and {tuple(cont.shape)}")
+        if len(bottoms) > 2 and (bottoms[2].shape[0] != N or bottoms[2].count_range(1) != self.w_xs.shape[1]):
+            raise ValueError(f"LSTM {self.name!r}: x_static needs shape [{N}, ...] of {self.w_xs.shape[1]} values, got "
+                             f"{tuple(bottoms[2].shape)}")
+        tops[0].reshape((T, N, self.H), self.dtype)
+        if self.h0 is None or tuple(self.h0.shape) != (N, self.H):
+            self.h0 = torch.zeros((N, self.H), dtype=self.dtype, device=self.device)
+            self.c0 = torch.zeros((N, self.H), dtype=torch.float32, device=self.device)
+
+    def reset(self):
+        """Forget the carried state: the next forward starts from h_0 = c_0 = 0."""
+        if self.h0 is not None:  # before the first reshape there is no state yet
+            self.h0.zero_()
+            self.c0.zero_()
+
+    @staticmethod
+    def _rows(b, rows, diff=False):
+        """The blob's values as [rows, count / rows] in Caffe's logical order."""
+        t = b.diff if diff else b.data
+        if b.is_image:
+            t = _to_logical(b, diff) if t.is_cuda else b.nchw(diff).contiguous()
+        return t.reshape(rows, -1)
+
+    def _operands(self, bottoms):
+        x, cont = bottoms[0], bottoms[1].data
+        T, N = x.shape[:2]
+        cont = _as(cont, torch.float32) if cont.is_cuda else cont.float()
+        xs = self._rows(bottoms[2], N) if len(bottoms) > 2 else None
+        return self._rows(x, T * N), cont.reshape(T, N), xs, self.w_xs.compute if xs is not None else None
+
+    def forward(self, bottoms, tops):
+        from .. import proto
+        x2, cont, xs, w_xs = self._operands(bottoms)
+        h, self.saved = ops.lstm_forward(x2, cont, self.w_xc.compute, self.b_c.data, self.w_hc.compute, self.h0, self.c0,
+                                         xs, w_xs, train=self.phase != proto.TEST)
+        tops[0].data = h
+
+    def backward(self, tops, propagate_down, bottoms):
+        if len(propagate_down) > 1 and propagate_down[1]:
+            raise ValueError(f"LSTM {self.name!r} cannot backpropagate to cont")
+        x2, cont, xs, w_xs = self._operands(bottoms)
+        grads, acc = [], []
+        for i, p in enumerate(self.params):  # accumulate unless this is the first write of a lazily cleared buffer
+            need = self.param_grads_needed(i)
+            grads.append(p.diff if need else None)
+            acc.append(not (need and self.grad_overwrite(i)))
+        if self.w_xs is None:
+            grads.insert(2, None), acc.insert(2, True)
+        need_dxs = len(bottoms) > 2 and bool(propagate_down[2])
+        dx, dxs = ops.lstm_backward(tops[0].diff, x2, cont, self.w_xc.compute, self.w_hc.compute, self.saved,
+                                    bool(propagate_down[0]), grads[0], grads[1], grads[3], xs, w_xs, grads[2], need_dxs,
+                                    tuple(acc))
+        for b, d in ((bottoms[0], dx if propagate_down[0] else None), (bottoms[-1], dxs if need_dxs else None)):
+            if d is None:
+                continue
+            d = d.to(b.dtype)
+            if b.is_image:
+                b.diff = _from_logical(d, b) if d.is_cuda else d.reshape(b.shape).permute(0, 2, 3, 1).contiguous()
+            else:
+                b.diff = d.reshape(b.data.shape)
+
+    def allow_force_backward(self, bottom_id: int) -> bool:
+        return bottom_id != 1
+
+
 @register("Python")
 class PythonLayer(Layer):
     """User-defined layer in Python (caffe/include/caffe/python_layer.hpp:14,

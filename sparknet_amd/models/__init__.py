@@ -1,4 +1,4 @@
 """Model zoo (DSL-built NetParameters + reference solver settings)."""
 from .zoo import (MODELS, alexnet, build, caffenet, cifar10_full, cifar10_quick, fast_rcnn, faster_rcnn, fcn8s, googlenet, lenet,  # noqa: F401
-                  mnasnet, mobilenet, resnet50, resnet_cifar, resnext, resnext50, se_resnet, se_resnet50, shufflenet,
+                  lrcn, mnasnet, mobilenet, resnet50, resnet_cifar, resnext, resnext50, se_resnet, se_resnet50, shufflenet,
                   solver_for, vgg16)

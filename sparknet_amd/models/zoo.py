@@ -24,6 +24,8 @@
   (or ROIAlign) of conv5 over given ROIs, fc6 / fc7, a SoftmaxWithLoss and a SmoothL1Loss head
 * ``faster_rcnn``    — not in the reference; Faster R-CNN (Ren et al. 2015): the same trunks under a region-proposal
   network; TRAIN is the stage-1 RPN net, TEST runs the Proposal layer (decode, top-k, NMS) into ROIPooling and the head
+* ``lrcn``           — not in the reference; LRCN (Donahue et al. 2015): the CaffeNet trunk through fc6 on every
+  frame, one LSTM (fused step kernels) over the T frames of a stream and a per-timestep classifier
 * ``se_resnet50``    — not in the reference; SE-ResNet-50 (Hu et al. 2018): ResNet-50 with a squeeze-and-
   excitation tail per block (global pool, two 1x1 convolutions, Sigmoid) gating the block output in an Axpy
 
@@ -37,7 +39,7 @@ from .. import proto
 from ..dsl import (AccuracyLayer, AxpyLayer, BatchNormLayer, ConcatLayer, ConvolutionLayer, DropoutLayer, EltwiseLayer,
                    Include, InnerProductLayer, LRNLayer, NetParam, Pooling, PoolingLayer, RDDLayer, ReLULayer,
                    ScaleLayer, ShuffleChannelLayer, SigmoidLayer, SoftmaxWithLoss, CropLayer, DeconvolutionLayer,
-                   ROIAlignLayer, ROIPoolingLayer, SmoothL1LossLayer, ProposalLayer, ReshapeLayer, SoftmaxLayer)
+                   ROIAlignLayer, ROIPoolingLayer, SmoothL1LossLayer, ProposalLayer, ReshapeLayer, SoftmaxLayer, LSTMLayer)
 from ..ops.spec import PoolSpec
 
 WB = [(1.0, 1.0), (2.0, 0.0)]   # weight / bias lr & decay mults used by the ImageNet models
@@ -409,6 +411,41 @@ def faster_rcnn(trunk="vgg16", classes=21, images=1, size=600, width=1.0, pre_nm
                _ip("cls_score", "fc7", classes, _g(0.01), _c(0.0)), _ip("bbox_pred", "fc7", 4 * classes, _g(0.001), _c(0.0)),
                SoftmaxLayer("cls_prob", ["cls_score"]))
     return NetParam("CaffeNet" if trunk == "caffenet" else "VGG_ILSVRC_16_layers", *L)
+
+
+def lrcn(T=16, N=24, classes=101, size=227, width=1.0, drop=0.5, trunk=True):
+    """LRCN (Donahue et al. 2015; layer and blob names of upstream's examples/LRCN_activity_recognition): not in
+    the reference.  Inputs ``data`` [T N, 3, size, size] with frame t of stream n at row t N + n, ``label`` [T, N]
+    and ``clip_markers`` [T, N] (0 where a stream starts, else 1).  The CaffeNet trunk through ``fc6`` runs on all
+    T N frames at once; ``reshape-data`` makes them [T, N, 4096] for ``lstm1`` (256 units; the step kernels of
+    csrc/kernels/lstm.hip), ``fc8-final`` classifies every timestep (axis 2) and the SoftmaxWithLoss takes the
+    scores and labels flattened to T N rows.  ``width`` scales the channel counts and the LSTM's units.
+    ``trunk=False`` is the recurrent head alone on stored fc6 features: ``fc6-reshape`` [T, N, 4096] is an input."""
+    ch = lambda n: max(8, int(n * width / 8 + 0.5) * 8)
+    fc8 = _ip("fc8-final", "lstm1", classes, _g(0.01), _c(0.0))
+    fc8.inner_product_param.axis = 2
+    head = [LSTMLayer("lstm1", ["fc6-reshape", "clip_markers"], ch(256),
+                      weight_filler={"type": "uniform", "min": -0.01, "max": 0.01}, bias_filler=_c(0.0)),
+            DropoutLayer("lstm1-drop", ["lstm1"], drop), fc8,
+            ReshapeLayer("reshape-score", ["fc8-final"], [-1, classes], top=["score"]),
+            ReshapeLayer("reshape-label", ["label"], [-1, 1], top=["label-flat"]),
+            SoftmaxWithLoss("loss", ["score", "label-flat"])]
+    if not trunk:
+        return NetParam("lstm_joints", RDDLayer("fc6-reshape", [T, N, ch(4096)]), RDDLayer("label", [T, N]),
+                        RDDLayer("clip_markers", [T, N]), *head)
+    return NetParam("lstm_joints", RDDLayer("data", [T * N, 3, size, size]), RDDLayer("label", [T, N]),
+                    RDDLayer("clip_markers", [T, N]),
+                    _conv("conv1", "data", 11, ch(96), stride=4, wf=_g(0.01), bf=_c(0.0)),
+                    _relu("relu1", "conv1"), _pool("pool1", "conv1", 3, 2), LRNLayer("norm1", ["pool1"], 5, 1e-4, 0.75),
+                    _conv("conv2", "norm1", 5, ch(256), pad=2, group=2, wf=_g(0.01), bf=_c(1.0)),
+                    _relu("relu2", "conv2"), _pool("pool2", "conv2", 3, 2), LRNLayer("norm2", ["pool2"], 5, 1e-4, 0.75),
+                    _conv("conv3", "norm2", 3, ch(384), pad=1, wf=_g(0.01), bf=_c(0.0)), _relu("relu3", "conv3"),
+                    _conv("conv4", "conv3", 3, ch(384), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu4", "conv4"),
+                    _conv("conv5", "conv4", 3, ch(256), pad=1, group=2, wf=_g(0.01), bf=_c(1.0)), _relu("relu5", "conv5"),
+                    _pool("pool5", "conv5", 3, 2),
+                    _ip("fc6", "pool5", ch(4096), _g(0.005), _c(1.0)), _relu("relu6", "fc6"),
+                    DropoutLayer("drop6", ["fc6"], drop),
+                    ReshapeLayer("reshape-data", ["fc6"], [T, N, -1], top=["fc6-reshape"]), *head)
 
 
 MSRA = {"type": "msra"}
@@ -792,6 +829,11 @@ def faster_rcnn_solver(net=None):  # the public stage-1 RPN solver of the altern
                    average_loss=100, max_iter=80000, momentum=0.9, weight_decay=5e-4)
 
 
+def lrcn_solver(net=None):  # upstream's lstm_solver_RGB.prototxt
+    return _solver(net or lrcn(), base_lr=0.001, lr_policy="step", gamma=0.1, stepsize=10000, display=20,
+                   max_iter=30000, momentum=0.9, weight_decay=0.005, clip_gradients=5.0)
+
+
 def resnext50_solver(net=None):  # ResNet-50's schedule
     return _solver(net or resnext50(), test_iter=[1000], test_interval=5000, base_lr=0.1, lr_policy="step",
                    gamma=0.1, stepsize=150000, display=20, max_iter=600000, momentum=0.9, weight_decay=1e-4)
@@ -811,7 +853,7 @@ MODELS = {
     "resnext50": (resnext50, resnext50_solver), "se_resnet50": (se_resnet50, se_resnet50_solver),
     "mnasnet": (mnasnet, mnasnet_solver), "shufflenet": (shufflenet, shufflenet_solver),
     "fcn8s": (fcn8s, fcn8s_solver), "fast_rcnn": (fast_rcnn, fast_rcnn_solver),
-    "faster_rcnn": (faster_rcnn, faster_rcnn_solver),
+    "faster_rcnn": (faster_rcnn, faster_rcnn_solver), "lrcn": (lrcn, lrcn_solver),
 }
 
 

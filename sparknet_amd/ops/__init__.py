@@ -165,6 +165,27 @@ def proposal(scores, deltas, im_info, anchors, feat_stride, min_size, pre_nms_to
                                                 pre_nms_topn, post_nms_topn, nms_thresh)
 
 
+def _lstm_hip(x2, cont, w_hc) -> bool:
+    """The step kernels (csrc/kernels/lstm.hip) serve these operands; otherwise ops.ref's fp32 loop over t (the
+    CPU, the fp32 device mode, H not a multiple of 8, SN_FEATURES=lstm_kernels=0)."""
+    return _gpu(x2) and _hipmod().lstm_ok(x2, cont, w_hc)
+
+
+def lstm_forward(x2, cont, w_xc, b_c, w_hc, h0, c0, xs=None, w_xs=None, train=True):
+    """The LSTM layer's forward over all T steps: (h [T, N, H], saved); h0 / c0 are replaced by h_T / c_T."""
+    impl = _hipmod() if _lstm_hip(x2, cont, w_hc) else ref
+    return impl.lstm_forward(x2, cont, w_xc, b_c, w_hc, h0, c0, xs, w_xs, train)
+
+
+def lstm_backward(dh, x2, cont, w_xc, w_hc, saved, need_dx, dw_xc=None, db=None, dw_hc=None, xs=None, w_xs=None,
+                  dw_xs=None, need_dxs=False, acc=(True, True, True, True)):
+    """Backward of lstm_forward by the route that ran it (only ops.ref saves the cont_t h_{t-1} rows in fp32; the
+    kernels save them in bf16, or not at all after a forward with train=False, which hip.lstm_backward refuses)."""
+    impl = ref if saved[2] is not None and saved[2].dtype == torch.float32 else _hipmod()
+    return impl.lstm_backward(dh, x2, cont, w_xc, w_hc, saved, need_dx, dw_xc, db, dw_hc, xs, w_xs, dw_xs, need_dxs,
+                              acc)
+
+
 def pool_backward(dy, x, s, aux=None, y=None, gate=False):
     """gate=True: x is a slope-0 in-place ReLU output whose backward is fused here (MAX
     pooling on the GPU encodes it in the forward's argmax mask)."""

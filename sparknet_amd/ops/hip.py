@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ..utils import features
 from .gemm import (EPI_BF16, EPI_F32, EPI_F32_ACC, ConvGeom, Dense, FlipW, Fp8Side, Im2col, colsum, fp8_side_output,
-                   gemm, linear_dgrad, linear_fwd, linear_wgrad, side_bytes)
+                   _pad8, gemm, linear_dgrad, linear_fwd, linear_wgrad, side_bytes)
 from .spec import POOL_AVE, POOL_MAX, ConvNdSpec, ConvSpec, PoolSpec
 
 call = _lib.call
@@ -769,6 +769,97 @@ def proposal(scores, deltas, im_info, anchors, feat_stride, min_size, pre_nms_to
     call(PROPOSAL_MASK, sboxes, cnt, mask, N, B, pre, float(nms_thresh))
     call(PROPOSAL_SCAN, sboxes, sscores, cnt, mask, rois, out, count, N, B, pre, post, float(nms_thresh))
     return rois, out, count
+
+
+LSTM_STEP_FWD, LSTM_STEP_BWD, LSTM_TRANSPOSE = "lstm_step_fwd", "lstm_step_bwd", "lstm_transpose"
+
+
+def lstm_ok(x2, cont, w_hc) -> bool:
+    """Operands the LSTM step kernels take (csrc/kernels/lstm.hip): a bf16 net (bf16 ``w_hc`` [4H, H], the
+    compute shadow; bf16 or fp32 ``x2`` [T N, D], any D that linear_forward takes), fp32 ``cont`` [T, N], H a
+    multiple of 8, T N 4H and 4H max(H, D) within 32-bit indexing, at most 65535 row tiles of 16.  The fp32 device mode never gets here
+    (ops.lstm_forward); an fp8 net keeps its LSTM in bf16.  The switch is read on every call
+    (SN_FEATURES=lstm_kernels=0)."""
+    if not (x2.dim() == 2 and cont.dim() == 2 and w_hc.dim() == 2 and w_hc.dtype == BF16 and cont.dtype == torch.float32
+            and x2.dtype in (BF16, torch.float32) and x2.device == cont.device == w_hc.device):
+        return False
+    (T, N), H = cont.shape, w_hc.shape[1]
+    return (T >= 1 and N >= 1 and H >= 8 and H % 8 == 0 and w_hc.shape[0] == 4 * H and x2.shape[0] == T * N
+            and x2.shape[1] >= 1 and T * N * 4 * H < 2 ** 31 and 4 * H * max(H, x2.shape[1]) < 2 ** 31
+            and T * N * x2.shape[1] < 2 ** 31 and -(-N // 16) <= 65535 and features.enabled("lstm_kernels"))
+
+
+def _project_f32(x2, w):
+    """x2 [M, K] . w [R, K]^T as fp32 [M, R] through the engine's fp32 epilogue (bf16 operands)."""
+    xp, wp = _pad8(as_bf16(x2), 1), _pad8(as_bf16(w), 1)
+    out = torch.empty((x2.shape[0], w.shape[0]), dtype=torch.float32, device=x2.device)
+    gemm(x2.shape[0], w.shape[0], xp.shape[1], Dense(xp, xp.shape[1], True), Dense(wp, wp.shape[1], True), out,
+         w.shape[0], epi=EPI_F32)
+    return out
+
+
+def lstm_forward(x2, cont, w_xc, b_c, w_hc, h0, c0, xs=None, w_xs=None, train=True):
+    """The LSTM layer's forward: ``x2`` [T N, D], ``cont`` [T, N] fp32, ``w_xc`` [4H, D], ``b_c`` [4H] fp32,
+    ``w_hc`` [4H, H], the carried state ``h0`` [N, H] bf16 / ``c0`` [N, H] fp32, optionally ``xs`` [N, Ds] with
+    ``w_xs`` [4H, Ds].  One product for the input projection (fp32 out), one for the static one, then one
+    lstm_step_fwd launch per timestep, which adds the bias itself (the engine's unsplit fp32 epilogue takes
+    none).  Returns (h [T, N, H] bf16, saved) with saved = (cells [T + 1, N, H] fp32 from c_0 on, the activated
+    gates [T, N, 4H] bf16, cont_t h_{t-1} [T, N, H] bf16), the last two None unless ``train``; ``h0`` and ``c0``
+    are then overwritten by h_T and c_T with device copies, so a captured iteration carries its state."""
+    if not lstm_ok(x2, cont, w_hc):
+        raise ValueError(f"lstm_forward: x {tuple(x2.shape)} {x2.dtype} / cont {tuple(cont.shape)} {cont.dtype} / W_hc "
+                         f"{tuple(w_hc.shape)} {w_hc.dtype} are not served by the LSTM step kernels")
+    (T, N), H, dev = cont.shape, w_hc.shape[1], x2.device
+    cont, w_hc, b_c = _c(cont), _c(w_hc), _c(b_c.float())
+    if h0.dtype != BF16 or c0.dtype != torch.float32 or tuple(h0.shape) != (N, H) or tuple(c0.shape) != (N, H):
+        raise ValueError(f"lstm_forward: state h0 {tuple(h0.shape)} {h0.dtype} / c0 {tuple(c0.shape)} {c0.dtype}")
+    xg = _project_f32(x2, w_xc)
+    xsg = _project_f32(xs, w_xs) if xs is not None else None
+    h = torch.empty((T, N, H), dtype=BF16, device=dev)
+    cells = torch.empty((T + 1, N, H), dtype=torch.float32, device=dev)
+    cells[0].copy_(c0)
+    gates = torch.empty((T, N, 4 * H), dtype=BF16, device=dev) if train else None
+    hc = torch.empty((T, N, H), dtype=BF16, device=dev) if train else None
+    xg3 = xg.view(T, N, 4 * H)
+    for t in range(T):
+        call(LSTM_STEP_FWD, h[t - 1] if t else h0, w_hc, xg3[t], b_c, xsg, cont[t], cells[t], h[t], cells[t + 1],
+             gates[t] if train else None, hc[t] if train else None, N, H)
+    h0.copy_(h[T - 1])
+    c0.copy_(cells[T])
+    return h, (cells, gates, hc)
+
+
+def lstm_backward(dh, x2, cont, w_xc, w_hc, saved, need_dx, dw_xc=None, db=None, dw_hc=None, xs=None, w_xs=None,
+                  dw_xs=None, need_dxs=False, acc=(True, True, True, True)):
+    """Backward of lstm_forward for the top gradient ``dh`` [T, N, H]: one lstm_step_bwd launch per timestep
+    from the last to the first (each forms its own recurrent gradient from dgates[t + 1] and a [H, 4H] copy of
+    ``w_hc`` transposed once here), then the engine: dW_xc, db_c and dx from one linear_backward over dgates
+    [T N, 4H], dW_hc from one weight-gradient product against the saved cont_t h_{t-1} rows, the static
+    projection's from dgates summed over T.  ``acc`` = accumulate (True) or store into (dw_xc, db, dw_xs, dw_hc),
+    the order of the layer's blobs.  Returns (dx [T N, D] bf16 or None, dxs [N, Ds] or None)."""
+    cells, gates, hc = saved
+    if gates is None:
+        raise ValueError("lstm_backward: the forward did not run with train=True")
+    (T, N), H, dev = cont.shape, w_hc.shape[1], dh.device
+    cont, dh = _c(cont), as_bf16(dh.reshape(T, N, H))
+    wt = torch.empty((H, 4 * H), dtype=BF16, device=dev)
+    call(LSTM_TRANSPOSE, _c(w_hc), wt, 4 * H, H)
+    dg = torch.empty((T, N, 4 * H), dtype=BF16, device=dev)
+    dc = torch.empty((N, H), dtype=torch.float32, device=dev)
+    for t in range(T - 1, -1, -1):
+        last = t == T - 1
+        call(LSTM_STEP_BWD, None if last else dg[t + 1], wt, None if last else cont[t + 1], dh[t], cont[t], gates[t],
+             cells[t + 1], cells[t], dc, dg[t], N, H)
+    dg2 = dg.view(T * N, 4 * H)
+    if dw_hc is not None:
+        linear_wgrad(dg2, hc.view(T * N, H), dw_hc, accumulate=acc[3])
+    dx = linear_backward(dg2, as_bf16(x2), as_bf16(w_xc), need_dx, dw_xc, db, dw_acc=acc[0], db_acc=acc[1])
+    dxs = None
+    if xs is not None and (dw_xs is not None or need_dxs):
+        from . import layers_hip
+        dgs = layers_hip.cast(layers_hip.axis_reduce(layers_hip.RED_SUM, dg, None, 1, T, N * 4 * H, 1).view(N, 4 * H), BF16)
+        dxs = linear_backward(dgs, as_bf16(xs), as_bf16(w_xs), need_dxs, dw_xs, None, dw_acc=acc[2])
+    return dx, dxs
 
 
 PATCH_DGRAD = "conv_patch_dgrad"

@@ -503,6 +503,60 @@ def proposal(scores, deltas, im_info, anchors, feat_stride, min_size, pre_nms_to
     return rois.reshape(-1, 5).to(dev), out_sc.reshape(-1, 1).to(dev), count.to(dev)
 
 
+# --- LSTM (upstream lstm_layer.cpp / lstm_unit_layer.cpp / recurrent_layer.cpp) -------------------------------
+
+def lstm_forward(x2, cont, w_xc, b_c, w_hc, h0, c0, xs=None, w_xs=None, train=True):
+    """The LSTM layer in fp32, a loop over t (the semantics of csrc/kernels/lstm.hip): pre = W_xc x_t + b_c
+    (+ W_xs xs) + W_hc (cont_t h_{t-1}); i, f, o = sigmoid, g = tanh over the 4H axis in that order; c_t = cont_t
+    f c_{t-1} + i g; h_t = o tanh(c_t).  ``x2`` [T N, D], ``cont`` [T, N], state ``h0`` / ``c0`` [N, H], overwritten by
+    h_T / c_T.  Returns (h [T, N, H] in h0's dtype, saved = (cells [T + 1, N, H], gates [T, N, 4H], cont_t h_{t-1}
+    [T, N, H]), all fp32)."""
+    (T, N), H = cont.shape, w_hc.shape[1]
+    cont, w_hc = cont.float(), w_hc.float()
+    xg = (x2.float() @ w_xc.float().t() + b_c.float()).reshape(T, N, 4 * H)
+    if xs is not None:
+        xg = xg + xs.float() @ w_xs.float().t()
+    h, cells, gates, hcs = h0.float(), [c0.float().clone()], [], []
+    hs = []
+    for t in range(T):
+        hc = cont[t, :, None] * h
+        pre = xg[t] + hc @ w_hc.t()
+        a = torch.cat([torch.sigmoid(pre[:, :3 * H]), torch.tanh(pre[:, 3 * H:])], 1)
+        c = cont[t, :, None] * a[:, H:2 * H] * cells[-1] + a[:, :H] * a[:, 3 * H:]
+        h = a[:, 2 * H:3 * H] * torch.tanh(c)
+        hs.append(h), cells.append(c), gates.append(a), hcs.append(hc)
+    h0.copy_(h)
+    c0.copy_(cells[-1])
+    return torch.stack(hs).to(h0.dtype), (torch.stack(cells), torch.stack(gates), torch.stack(hcs))
+
+
+def lstm_backward(dh, x2, cont, w_xc, w_hc, saved, need_dx, dw_xc=None, db=None, dw_hc=None, xs=None, w_xs=None,
+                  dw_xs=None, need_dxs=False, acc=(True, True, True, True)):
+    """Backward of lstm_forward for the top gradient ``dh`` [T, N, H]; ``acc``: accumulate or store into (dw_xc,
+    db, dw_xs, dw_hc).  No gradient reaches the state a forward started from.  Returns (dx [T N, D], dxs)."""
+    cells, gates, hcs = saved
+    (T, N), H = cont.shape, w_hc.shape[1]
+    cont, w_hc, dh = cont.float(), w_hc.float(), dh.float().reshape(T, N, H)
+    dg = torch.zeros((T, N, 4 * H), dtype=torch.float32, device=dh.device)
+    dc = torch.zeros((N, H), dtype=torch.float32, device=dh.device)
+    for t in range(T - 1, -1, -1):
+        d = dh[t] + (cont[t + 1, :, None] * (dg[t + 1] @ w_hc) if t < T - 1 else 0)
+        i, f, o, g = gates[t].float().split(H, 1)
+        ct, tc = cont[t, :, None], torch.tanh(cells[t + 1])
+        dc = dc + d * o * (1 - tc * tc)
+        dg[t] = torch.cat([dc * g * i * (1 - i), dc * ct * cells[t] * f * (1 - f), d * tc * o * (1 - o),
+                           dc * i * (1 - g * g)], 1)
+        dc = dc * ct * f
+    dg2 = dg.reshape(T * N, 4 * H)
+    if dw_hc is not None:
+        _acc(dw_hc, dg2.t() @ hcs.float().reshape(T * N, H), acc[3])
+    dx = linear_backward(dg2, x2.float(), w_xc, need_dx, dw_xc, db, dw_acc=acc[0], db_acc=acc[1])
+    dxs = None
+    if xs is not None and (dw_xs is not None or need_dxs):
+        dxs = linear_backward(dg.sum(0), xs.float(), w_xs, need_dxs, dw_xs, None, dw_acc=acc[2])
+    return dx, dxs
+
+
 def relu_forward(x, slope=0.0):
     xf = x.float()
     return torch.where(xf > 0, xf, xf * slope).to(x.dtype)

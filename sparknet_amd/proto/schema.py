@@ -116,6 +116,8 @@ MESSAGES: dict[str, tuple[dict, list]] = {
         o("power_param", 122, "PowerParameter"), o("prelu_param", 131, "PReLUParameter"),
         o("python_param", 130, "PythonParameter"), o("reduction_param", 136, "ReductionParameter"),
         o("relu_param", 123, "ReLUParameter"), o("reshape_param", 133, "ReshapeParameter"),
+        # field numbers not verified against upstream caffe.proto (docs/COMPONENTS.md)
+        o("recurrent_param", 146, "RecurrentParameter"),
         o("shuffle_channel_param", 164, "ShuffleChannelParameter"),  # this project's own field number
         o("roi_align_param", 165, "ROIAlignParameter"),  # this project's own field number
         o("proposal_param", 166, "ProposalParameter"),  # this project's own field number
@@ -217,6 +219,9 @@ MESSAGES: dict[str, tuple[dict, list]] = {
                                o("min_size", 3, "float", 16), r("ratio", 4, "float"), r("scale", 5, "float"),
                                o("pre_nms_topn", 6, "uint32", 6000), o("post_nms_topn", 7, "uint32", 300),
                                o("nms_thresh", 8, "float", 0.7)]),
+    "RecurrentParameter": ({}, [o("num_output", 1, "uint32", 0), o("weight_filler", 2, "FillerParameter"),
+                                o("bias_filler", 3, "FillerParameter"), o("debug_info", 4, "bool", False),
+                                o("expose_hidden", 5, "bool", False)]),
     "ReshapeParameter": ({}, [o("shape", 1, "BlobShape"), o("axis", 2, "int32", 0), o("num_axes", 3, "int32", -1)]),
     "SigmoidParameter": ({"Engine": ENGINE}, [o("engine", 1, "SigmoidParameter.Engine", "DEFAULT")]),
     "SliceParameter": ({}, [o("axis", 3, "int32", 1), r("slice_point", 2, "uint32"), o("slice_dim", 1, "uint32", 1)]),

@@ -44,6 +44,7 @@ DEFAULTS = {
     "deconv_dw": True,          # upsampling kernels for depthwise Deconvolution layers, strides up to 8, windows up to 16, any C (FCN; 0: per-channel dcol GEMM + col2im loop)
     "roi_kernels": True,        # ROIPooling / ROIAlign kernels on the NHWC storage (Fast R-CNN; 0: the tensor code of ops.ref on the device, which reads the ROIs on the host and cannot be captured)
     "proposal_kernels": True,   # decode / top-k select / bitmask NMS / greedy scan kernels of the Proposal layer (Faster R-CNN; 0: the tensor code of ops.ref, whose NMS loop runs on the host and cannot be captured)
+    "lstm_kernels": True,       # fused LSTM step kernels, one launch per timestep and direction, H a multiple of 8 (LRCN; 0: the fp32 tensor loop of ops.ref on the device)
     "conv_patch": True,         # patch-resident data gradient of 5x5 grouped convs, 128 -> 48 channels per group (CaffeNet conv2; 0: implicit grouped GEMM)
     "conv_tstride": True,       # phase-decomposed data gradient of dense stride-2 convs, windows up to 4x4 (0: fp32 dcol GEMM + col2im)
     # per-image, per-channel kernels (csrc/kernels/se.hip)
